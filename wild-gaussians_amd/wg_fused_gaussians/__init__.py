@@ -20,6 +20,13 @@ no host synchronisation (the torch code runs six boolean-mask index operations, 
     add_densification_stats(radii, viewspace_points.grad, model.xyz_grad, model.denom, max_radii2D=model.max_radii2D,
                             xyz_gradient_accum_abs=model.xyz_gradient_accum_abs,
                             xyz_gradient_accum_abs_max=model.xyz_gradient_accum_abs_max)
+
+GaussianModel.compute_3D_filter (method.py:1140-1190: a Python loop over all training cameras) as one kernel over all (Gaussian,
+camera) pairs (include/wg_filter3d.h):
+
+    from wg_fused_gaussians import CameraTable, compute_3D_filter
+    table = CameraTable(train_cameras)             # once: the training cameras do not change
+    filter_3D = compute_3D_filter(model.xyz, table)   # [P, 1]
 """
 from __future__ import annotations
 
@@ -262,3 +269,82 @@ def eval_sh(deg, sh: torch.Tensor, dirs: torch.Tensor) -> torch.Tensor:
     lead = sh.shape[:-2]
     out = _EvalSH.apply(deg, sh.reshape(-1, 3, sh.shape[-1]).contiguous(), dirs.reshape(-1, 3).contiguous())
     return out.reshape(*lead, 3)
+
+
+# ---- fused computation of filter_3D (include/wg_filter3d.h, csrc/activations.hip) ---------------------------------
+class _Filter3dCamera(C.Structure):   # wg_filter3d_camera
+    _fields_ = [("w2c", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("width", C.c_float), ("height", C.c_float)]
+
+
+_lib.wg_compute_3d_filter.restype = _i
+_lib.wg_compute_3d_filter.argtypes = [_i, _vp, _i, _vp, C.c_float, _vp, _vp, _vp]
+
+
+def pack_cameras(poses, intrinsics, image_sizes):
+    """Host side of ``CameraTable``: -> (table, focal_length) with ``table`` a float32 [C, 16] array of ``wg_filter3d_camera`` records and
+    ``focal_length`` the largest fx of all cameras (0.0 without cameras).  The world-to-camera transform is the reference's
+    (wildgaussians/method.py:1152-1161): ``np.linalg.inv`` of the 4x4 pose in the pose's own dtype, then float32."""
+    import numpy as np
+    poses, intrinsics, image_sizes = np.asarray(poses), np.asarray(intrinsics), np.asarray(image_sizes)
+    if poses.ndim == 2:   # one camera (Cameras[i])
+        poses, intrinsics, image_sizes = poses[None], intrinsics[None], image_sizes[None]
+    n = poses.shape[0]
+    if poses.shape[1:] != (3, 4) or intrinsics.shape != (n, 4) or image_sizes.shape != (n, 2):
+        raise RuntimeError("wg_fused_gaussians: expected poses [C, 3, 4], intrinsics [C, 4] and image_sizes [C, 2]")
+    c2w = np.concatenate([poses, np.broadcast_to(np.array([[0, 0, 0, 1]], dtype=poses.dtype), (n, 1, 4))], axis=1)
+    w2c = np.linalg.inv(c2w)   # one LAPACK solve per matrix, as in the reference's loop
+    table = np.empty((n, 16), dtype=np.float32)
+    table[:, :12] = w2c[:, :3, :].reshape(n, 12)
+    table[:, 12:14] = intrinsics[:, :2]
+    table[:, 14:16] = image_sizes
+    assert table.shape[1] * table.itemsize == C.sizeof(_Filter3dCamera)
+    return table, (float(np.float32(intrinsics[:, 0].max())) if n else 0.0)
+
+
+class CameraTable:
+    """The training cameras as ``compute_3D_filter`` reads them, built once (they do not change during a run): the device array of
+    64-byte records, ``focal_length`` (the largest fx) and the call's 8-byte workspace.  ``cameras``: the reference's ``Cameras`` object
+    (numpy attributes ``poses`` [C, 3, 4] camera-to-world, ``intrinsics`` [C, 4], ``image_sizes`` [C, 2]) or a tuple of those three
+    arrays.  A table serves one stream at a time (the workspace is its own)."""
+
+    def __init__(self, cameras, device=None):
+        arrays = cameras if isinstance(cameras, (tuple, list)) else (cameras.poses, cameras.intrinsics, cameras.image_sizes)
+        if len(arrays) != 3 or arrays[2] is None:
+            raise RuntimeError("wg_fused_gaussians: CameraTable needs poses, intrinsics and image_sizes")
+        self.cameras = cameras   # keeps the object alive: callers key tables by its identity
+        self.host, self.focal_length = pack_cameras(*arrays)
+        self.num_cameras = self.host.shape[0]
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("wg_fused_gaussians: a CameraTable lives on a HIP device (there is no CPU path)")
+        self.table = torch.from_numpy(self.host).to(self.device)
+        self.workspace = torch.empty(8, dtype=torch.uint8, device=self.device)
+
+
+@torch.no_grad()
+def compute_3D_filter(xyz, cameras, out=None):
+    """``GaussianModel.compute_3D_filter`` (wildgaussians/method.py:1140-1190) as one kernel over all (Gaussian, camera) pairs + one for
+    the fill and the scale, stream-ordered, without a host synchronisation: -> ``filter_3D`` [P, 1] float32 (``out`` when given, written
+    in place).  ``xyz`` [P, 3] float32 on a HIP device; ``cameras``: a ``CameraTable`` (build it once) or anything one can be built from
+    (then built per call).  Where no camera sees any point (the reference raises) every value is 100000 / focal_length * sqrt(0.2)."""
+    if not (torch.is_tensor(xyz) and xyz.is_cuda and xyz.dtype == torch.float32):
+        raise RuntimeError("wg_fused_gaussians: xyz must be a float32 tensor on a HIP device (there is no CPU path)")
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise RuntimeError("wg_fused_gaussians: xyz must be [P, 3]")
+    table = cameras if isinstance(cameras, CameraTable) else CameraTable(cameras, device=xyz.device)
+    if table.device != xyz.device:
+        raise RuntimeError("wg_fused_gaussians: the CameraTable and xyz are on different devices")
+    x = xyz.detach().contiguous()
+    P = x.shape[0]
+    if out is None:
+        out = torch.empty((P, 1), device=x.device, dtype=torch.float32)
+    else:
+        if not (out.is_cuda and out.device == x.device and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == P):
+            raise RuntimeError(f"wg_fused_gaussians: out must be a contiguous float32 tensor of {P} elements on xyz's device")
+        torch.autograd.graph.increment_version(out)   # written behind torch's back (as FusedAdam says it: the binding's geometry reuse reads it)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    with torch.cuda.device(x.device):
+        _native._check(_lib.wg_compute_3d_filter(P, x.data_ptr(), table.num_cameras, table.table.data_ptr() if table.num_cameras else None,
+                                                 table.focal_length, out.data_ptr(), table.workspace.data_ptr(), stream),
+                       "wg_compute_3d_filter")
+    return out.view(P, 1)

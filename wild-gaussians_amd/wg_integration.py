@@ -17,6 +17,10 @@ needs the few-line edits INTEGRATION.md lists.  What IS swapped, each with the r
   activations           `GaussianModel.get_gaussians` (method.py:1060-1086)          -> wg_fused_gaussians.activate (same dict)
   eval_sh               `method.eval_sh` (method.py:493-548, called at :1564, :1597) -> wg_fused_gaussians.eval_sh; calls it does not cover
                         (degree 4, a channel count other than 3, CPU tensors) go to the original function
+  filter_3d             (OFF by default, unlike the switches above: a visibility decision at a screen border or at the near limit can fall
+                        the other way than torch's matmul makes it fall, and callers' pinned results must not move unasked)
+                        `GaussianModel.compute_3D_filter` (method.py:1140-1190) -> wg_fused_gaussians.compute_3D_filter with one
+                        CameraTable per `cameras` object (built at its first call); the buffer is registered as the reference does
   edited_module         (off by default) `GaussianModel._render_internal` -> the one of a module the INTEGRATOR supplies: a copy of the caller with
                         INTEGRATION.md section 5's "two_colour" or "two_tone" edit applied (the documented diff is the deliverable; this package
                         does not rewrite anybody's source -- tests/real_caller/render_edits.py is the test tool that builds such a module in memory)
@@ -30,7 +34,7 @@ import torch
 
 
 def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True, densification_stats: bool = True, activations: bool = True,
-                 eval_sh: bool = True, geometry_reuse: bool = True, edited_module=None):
+                 eval_sh: bool = True, geometry_reuse: bool = True, edited_module=None, filter_3d: bool = False):
     """-> a function that restores everything that was replaced.  `model`: an already constructed GaussianModel (e.g.
     `WildGaussians(...).model`) whose existing optimizer should be adopted too.
     edited_module (default None): a module object holding a copy of the caller with INTEGRATION.md section 5's edit of `_render_internal`
@@ -84,6 +88,19 @@ def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True
                 return orig_eval_sh(deg, sh, dirs)   # the caller's own code, not a fallback of this library
             return FG.eval_sh(d, sh, dirs)
         swap(method_module, "eval_sh", fused_eval_sh)
+
+    if filter_3d:
+        tables = {}   # id(cameras) -> CameraTable; the table holds a reference to its cameras object, so the id stays that object's
+
+        def compute_3D_filter(self, cameras):
+            xyz = self.xyz
+            table = tables.get(id(cameras))
+            if table is None or table.cameras is not cameras or table.device != xyz.device:
+                table = tables[id(cameras)] = FG.CameraTable(cameras, device=xyz.device)
+            filter_3D = FG.compute_3D_filter(xyz, table).to(dtype=self.filter_3D.dtype, device=self.filter_3D.device)
+            del self.filter_3D   # as the reference registers its result (method.py:1188-1190)
+            self.register_buffer("filter_3D", filter_3D)
+        swap(GM, "compute_3D_filter", compute_3D_filter)
 
     if edited_module is not None:
         edited = edited_module
