@@ -27,4 +27,8 @@ int wg_densification_stats(int P, const int* radii, const float* viewspace_grad,
 #ifdef __cplusplus
 }
 #endif
+
+/* The step that consumes these statistics -- clone, split and prune in one pass, its exact quantile, reset_opacity -- is declared in a
+ * header of its own, part of this one. */
+#include "wg_densify_prune.h"
 #endif

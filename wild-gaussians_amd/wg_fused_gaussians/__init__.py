@@ -27,6 +27,13 @@ camera) pairs (include/wg_filter3d.h):
     from wg_fused_gaussians import CameraTable, compute_3D_filter
     table = CameraTable(train_cameras)             # once: the training cameras do not change
     filter_3D = compute_3D_filter(model.xyz, table)   # [P, 1]
+
+GaussianModel.densify_and_prune and reset_opacity (method.py:1249-1468) as one plan, one host read and one gather over all arrays, with an
+exact quantile that has no 2^24-element limit (include/wg_densify_prune.h):
+
+    from wg_fused_gaussians import densify_and_prune, reset_opacity, quantile
+    res = densify_and_prune(tensors, adam_state, stats, max_grad=..., min_opacity=..., extent=..., percent_dense=...,
+                            enable_size_pruning=..., use_abs_gradient=...)   # res.tensors, res.adam_state, res.stats, res.counts, res.Q, res.origin
 """
 from __future__ import annotations
 
@@ -348,3 +355,186 @@ def compute_3D_filter(xyz, cameras, out=None):
                                                  table.focal_length, out.data_ptr(), table.workspace.data_ptr(), stream),
                        "wg_compute_3d_filter")
     return out.view(P, 1)
+
+
+# ---- fused densify-and-prune, exact quantile, reset_opacity (include/wg_densify_prune.h, csrc/densify.hip) -------------------------
+class _DensifyParams(C.Structure):   # wg_densify_params
+    _fields_ = [("max_grad", C.c_float), ("min_opacity", C.c_float), ("dense_threshold", C.c_float), ("size_threshold", C.c_float),
+                ("enable_size_pruning", C.c_int32), ("use_abs_gradient", C.c_int32)]
+
+
+class _DensifyCounts(C.Structure):   # wg_densify_counts
+    _fields_ = [("n_out", C.c_int64 * 4), ("n_cloned", C.c_int64), ("n_split", C.c_int64), ("n_pruned", C.c_int64), ("n_hot", C.c_int64),
+                ("ratio", C.c_float), ("Q", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class _DensifyArray(C.Structure):   # wg_densify_array
+    _fields_ = [("src", _vp), ("dst", _vp), ("row_floats", C.c_int32), ("role", C.c_int32)]
+
+
+_DP_COPY, _DP_ZERO_NEW, _DP_XYZ, _DP_SCALES = 0, 1, 2, 3
+_DP_MAX_ARRAYS = 48
+_lib.wg_densify_scratch_bytes.restype = C.c_size_t
+_lib.wg_densify_scratch_bytes.argtypes = [C.c_int64]
+_lib.wg_quantile.restype = _i
+_lib.wg_quantile.argtypes = [C.c_int64, _vp, C.c_double, _vp, _vp, _vp]
+_lib.wg_densify_plan.restype = _i
+_lib.wg_densify_plan.argtypes = [C.c_int64, C.POINTER(_DensifyParams)] + [_vp] * 8
+_lib.wg_densify_apply.restype = _i
+_lib.wg_densify_apply.argtypes = [C.c_int64, C.POINTER(_DensifyCounts), _vp, _i, C.POINTER(_DensifyArray)] + [_vp] * 6
+_lib.wg_reset_opacity.restype = _i
+_lib.wg_reset_opacity.argtypes = [C.c_int64] + [_vp] * 7
+
+
+def _no_capture(what):
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"wg_fused_gaussians.{what} is not supported inside a stream capture: the output size is data-dependent")
+
+
+def _rows(t, P, name):
+    """A contiguous float32 HIP tensor whose leading dimension is the P Gaussians."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+        raise RuntimeError(f"wg_fused_gaussians: {name} must be a float32 tensor on a HIP device (there is no CPU path)")
+    if t.dim() < 1 or t.shape[0] != P:
+        raise RuntimeError(f"wg_fused_gaussians: {name} must have {P} rows")
+    return t.detach().contiguous()
+
+
+@torch.no_grad()
+def quantile(values, q):
+    """``torch.quantile(values.reshape(-1), q)`` (linear interpolation) by an exact radix selection, without torch's limit of 2^24 elements:
+    -> a 0-dim float32 tensor on the device, no host synchronisation.  Above 2^24 elements the rank is formed in float64
+    (include/wg_densify_prune.h).  NaN-free float32 values on a HIP device."""
+    if not (torch.is_tensor(values) and values.is_cuda and values.dtype == torch.float32):
+        raise RuntimeError("wg_fused_gaussians: values must be a float32 tensor on a HIP device (there is no CPU path)")
+    q = float(q)
+    if not 0.0 <= q <= 1.0:
+        raise RuntimeError("wg_fused_gaussians: quantile() q must be in [0, 1]")
+    v = values.detach().contiguous().reshape(-1)
+    if v.numel() == 0:
+        raise RuntimeError("wg_fused_gaussians: quantile() of an empty tensor")
+    out = torch.empty((), device=v.device, dtype=torch.float32)
+    scratch = torch.empty(_lib.wg_densify_scratch_bytes(0), device=v.device, dtype=torch.uint8)
+    with torch.cuda.device(v.device):
+        _native._check(_lib.wg_quantile(v.numel(), v.data_ptr(), q, out.data_ptr(), scratch.data_ptr(),
+                                        torch.cuda.current_stream(v.device).cuda_stream), "wg_quantile")
+    return out
+
+
+class DensifyResult:
+    """What ``densify_and_prune`` returns: ``tensors`` / ``adam_state`` / ``stats`` (dicts shaped like the inputs, P_new rows), ``counts`` =
+    (n_cloned, n_split_parents, n_pruned) as the reference returns them, ``Q`` (None without use_abs_gradient) and ``ratio`` (floats),
+    ``n_hot``, ``n_out`` (rows per kind) and ``origin`` (int32 [P_new, 2]: source index, kind 0 original / 1 clone / 2, 3 children)."""
+    __slots__ = ("tensors", "adam_state", "stats", "counts", "Q", "ratio", "n_hot", "n_out", "origin", "noise")
+
+
+@torch.no_grad()
+def densify_and_prune(tensors, adam_state, stats, *, max_grad, min_opacity, extent, percent_dense, enable_size_pruning, use_abs_gradient,
+                      noise=None, generator=None):
+    """``GaussianModel.densify_and_prune`` (wildgaussians/method.py:1280-1468) in one GPU pass: a plan (decisions, exact quantile, offsets),
+    ONE host wait for the new count, and one gather that moves every array once.
+
+    ``tensors``: name -> [P, ...] raw parameter; "xyz", "scales", "rotations" and "opacities" are required, everything else is copied.
+    ``adam_state``: name -> (exp_avg, exp_avg_sq) or a dict holding those two keys (torch's optimizer state) or None; copied for surviving
+    originals, zero for new rows.  ``stats``: name -> per-Gaussian buffer ([P] or [P, 1]); "xyz_grad", "denom" and, with use_abs_gradient,
+    "xyz_gradient_accum_abs" drive the decisions; all are carried like the moments (the reference does not reset them).
+    ``noise``: the [2 S, 3] standard-normal draw of the split, copy-major; None: ``torch.randn`` on the device with ``generator``, drawn
+    after S is known.  Inputs are left untouched.  -> ``DensifyResult``."""
+    for k in ("xyz", "scales", "rotations", "opacities"):
+        if k not in tensors:
+            raise RuntimeError(f"wg_fused_gaussians.densify_and_prune: tensors[{k!r}] is required")
+    for k in ("xyz_grad", "denom") + (("xyz_gradient_accum_abs",) if use_abs_gradient else ()):
+        if stats.get(k) is None:
+            raise RuntimeError(f"wg_fused_gaussians.densify_and_prune: stats[{k!r}] is required")
+    P = tensors["xyz"].shape[0]
+    dev = tensors["xyz"].device
+    src = {k: _rows(t, P, k) for k, t in tensors.items()}
+    _no_capture("densify_and_prune")
+    for k, cols in (("xyz", 3), ("scales", 3), ("rotations", 4), ("opacities", 1)):
+        if src[k].numel() != P * cols:
+            raise RuntimeError(f"wg_fused_gaussians.densify_and_prune: {k} must be [P, {cols}]")
+    moments = {}
+    for k, st in (adam_state or {}).items():
+        if st is None or k not in src:
+            continue
+        m, v = (st["exp_avg"], st["exp_avg_sq"]) if isinstance(st, dict) else st
+        m, v = _rows(m, P, k + ".exp_avg"), _rows(v, P, k + ".exp_avg_sq")
+        if m.shape != src[k].shape or v.shape != src[k].shape:
+            raise RuntimeError(f"wg_fused_gaussians.densify_and_prune: the moments of {k} must be shaped like it")
+        moments[k] = (m, v)
+    bufs = {k: _rows(t, P, k) for k, t in stats.items() if t is not None}
+    for k, t in bufs.items():
+        if t.numel() != P:
+            raise RuntimeError(f"wg_fused_gaussians.densify_and_prune: stats[{k!r}] must hold one float per Gaussian")
+    if any(t.device != dev for t in list(src.values()) + list(bufs.values()) + [x for mv in moments.values() for x in mv]):
+        raise RuntimeError("wg_fused_gaussians.densify_and_prune: all tensors must be on one device")
+    # thresholds as the reference's comparisons see them: Python forms the products in double, the float32 tensor meets them as float32
+    prm = _DensifyParams(float(max_grad), float(min_opacity), float(percent_dense) * float(extent), 0.1 * float(extent),
+                         int(bool(enable_size_pruning)), int(bool(use_abs_gradient)))
+    scratch = torch.empty(max(_lib.wg_densify_scratch_bytes(P), 1), device=dev, dtype=torch.uint8)
+    mailbox = torch.zeros(C.sizeof(_DensifyCounts), dtype=torch.uint8).pin_memory()
+    stream = torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev):
+        _native._check(_lib.wg_densify_plan(P, C.byref(prm), bufs["xyz_grad"].data_ptr(), bufs["denom"].data_ptr(),
+                                            bufs["xyz_gradient_accum_abs"].data_ptr() if use_abs_gradient else None,
+                                            src["scales"].data_ptr(), src["opacities"].data_ptr(), scratch.data_ptr(), mailbox.data_ptr(),
+                                            stream.cuda_stream), "wg_densify_plan")
+        stream.synchronize()   # the call's only host wait: the new count
+        counts = _DensifyCounts.from_buffer_copy(mailbox.numpy().tobytes())
+        n_out = [int(x) for x in counts.n_out]
+        n_new, S = sum(n_out), int(counts.n_split)
+        if noise is None:
+            noise = torch.randn((2 * S, 3), device=dev, dtype=torch.float32, generator=generator)
+        else:
+            if not (torch.is_tensor(noise) and noise.is_cuda and noise.dtype == torch.float32 and tuple(noise.shape) == (2 * S, 3)):
+                raise RuntimeError(f"wg_fused_gaussians.densify_and_prune: noise must be a float32 [{2 * S}, 3] tensor on the device "
+                                   f"(2 x {S} split Gaussians)")
+            noise = noise.contiguous()
+        new = lambda t: torch.empty((n_new,) + tuple(t.shape[1:]), device=dev, dtype=torch.float32)  # noqa: E731
+        res = DensifyResult()
+        res.tensors = {k: new(t) for k, t in src.items()}
+        res.adam_state = {k: (new(m), new(v)) for k, (m, v) in moments.items()}
+        res.stats = {k: new(t) for k, t in bufs.items()}
+        res.origin = torch.empty((n_new, 2), device=dev, dtype=torch.int32)
+        table = []
+        for k, t in src.items():
+            role = _DP_XYZ if k == "xyz" else _DP_SCALES if k == "scales" else _DP_COPY
+            table.append(_DensifyArray(t.data_ptr(), res.tensors[k].data_ptr(), t.numel() // max(P, 1), role))
+            if k in moments:
+                for s_, d_ in zip(moments[k], res.adam_state[k]):
+                    table.append(_DensifyArray(s_.data_ptr(), d_.data_ptr(), t.numel() // max(P, 1), _DP_ZERO_NEW))
+        for k, t in bufs.items():
+            table.append(_DensifyArray(t.data_ptr(), res.stats[k].data_ptr(), 1, _DP_ZERO_NEW))
+        if P and n_new:
+            for lo in range(0, len(table), _DP_MAX_ARRAYS):   # one launch for up to 48 arrays (the reference's model has 27)
+                part = table[lo:lo + _DP_MAX_ARRAYS]
+                arr = (_DensifyArray * len(part))(*part)
+                _native._check(_lib.wg_densify_apply(P, C.byref(counts), scratch.data_ptr(), len(part), arr, src["xyz"].data_ptr(),
+                                                     src["scales"].data_ptr(), src["rotations"].data_ptr(), noise.data_ptr(),
+                                                     res.origin.data_ptr(), stream.cuda_stream), "wg_densify_apply")
+    res.counts = (int(counts.n_cloned), S, int(counts.n_pruned))
+    res.Q = float(counts.Q) if use_abs_gradient else None
+    res.ratio, res.n_hot, res.n_out, res.noise = float(counts.ratio), int(counts.n_hot), tuple(n_out), noise
+    return res
+
+
+@torch.no_grad()
+def reset_opacity(opacities, scales, filter_3D, exp_avg=None, exp_avg_sq=None):
+    """``GaussianModel.reset_opacity``'s arithmetic (wildgaussians/method.py:1252-1266) as one elementwise kernel: -> the new raw opacities
+    (a new tensor shaped like ``opacities``); ``exp_avg`` / ``exp_avg_sq`` (the opacity moments), when given, are zeroed in place."""
+    P = opacities.shape[0] if torch.is_tensor(opacities) and opacities.dim() else 0
+    o, s, f = _rows(opacities, P, "opacities"), _rows(scales, P, "scales"), _rows(filter_3D, P, "filter_3D")
+    if o.numel() != P or s.numel() != 3 * P or f.numel() != P:
+        raise RuntimeError("wg_fused_gaussians.reset_opacity: expected opacities [P, 1], scales [P, 3] and filter_3D [P, 1]")
+    for name, t in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        if t is not None:
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == P and t.device == o.device):
+                raise RuntimeError(f"wg_fused_gaussians.reset_opacity: {name} must be a contiguous float32 tensor of {P} elements on the device")
+            torch.autograd.graph.increment_version(t)
+    out = torch.empty_like(o)
+    with torch.cuda.device(o.device):
+        _native._check(_lib.wg_reset_opacity(P, o.data_ptr(), s.data_ptr(), f.data_ptr(), out.data_ptr(),
+                                             None if exp_avg is None else exp_avg.data_ptr(),
+                                             None if exp_avg_sq is None else exp_avg_sq.data_ptr(),
+                                             torch.cuda.current_stream(o.device).cuda_stream), "wg_reset_opacity")
+    return out

@@ -21,6 +21,13 @@ needs the few-line edits INTEGRATION.md lists.  What IS swapped, each with the r
                         the other way than torch's matmul makes it fall, and callers' pinned results must not move unasked)
                         `GaussianModel.compute_3D_filter` (method.py:1140-1190) -> wg_fused_gaussians.compute_3D_filter with one
                         CameraTable per `cameras` object (built at its first call); the buffer is registered as the reference does
+  densify               (OFF by default, like filter_3d and for the same reason: a clone / split / prune decision that sits within an ulp of its
+                        threshold can fall the other way than torch's `exp` / `sigmoid` make it fall)
+                        `GaussianModel.densify_and_prune` (method.py:1420-1468, with _densify_and_clone, _densify_and_split,
+                        _densification_postfix, _prune_points) -> wg_fused_gaussians.densify_and_prune: one plan, one host wait, one gather;
+                        parameters and buffers are re-registered and `optimizer.state` re-keyed as the reference does (a new nn.Parameter
+                        per group, the state moved to it).  `GaussianModel.reset_opacity` (method.py:1249-1278) ->
+                        wg_fused_gaussians.reset_opacity.  The split's draw is torch.randn on the device
   edited_module         (off by default) `GaussianModel._render_internal` -> the one of a module the INTEGRATOR supplies: a copy of the caller with
                         INTEGRATION.md section 5's "two_colour" or "two_tone" edit applied (the documented diff is the deliverable; this package
                         does not rewrite anybody's source -- tests/real_caller/render_edits.py is the test tool that builds such a module in memory)
@@ -34,7 +41,7 @@ import torch
 
 
 def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True, densification_stats: bool = True, activations: bool = True,
-                 eval_sh: bool = True, geometry_reuse: bool = True, edited_module=None, filter_3d: bool = False):
+                 eval_sh: bool = True, geometry_reuse: bool = True, edited_module=None, filter_3d: bool = False, densify: bool = False):
     """-> a function that restores everything that was replaced.  `model`: an already constructed GaussianModel (e.g.
     `WildGaussians(...).model`) whose existing optimizer should be adopted too.
     edited_module (default None): a module object holding a copy of the caller with INTEGRATION.md section 5's edit of `_render_internal`
@@ -101,6 +108,50 @@ def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True
             del self.filter_3D   # as the reference registers its result (method.py:1188-1190)
             self.register_buffer("filter_3D", filter_3D)
         swap(GM, "compute_3D_filter", compute_3D_filter)
+
+    if densify:
+        def densify_and_prune(self, max_grad, min_opacity, extent, enable_size_pruning, skyradius=None):
+            del skyradius  # unused, as in the reference
+            assert self.optimizer is not None, "Not set up for training"
+            props = [n for n in self._dynamically_sized_props if getattr(self, n, None) is not None]
+            groups = {g["name"]: g for g in self.optimizer.param_groups if g.get("name") in props}
+            state = {n: self.optimizer.state.get(g["params"][0], None) for n, g in groups.items()}
+            state = {n: st if st is not None and "exp_avg" in st else None for n, st in state.items()}
+            res = FG.densify_and_prune({n: g["params"][0] for n, g in groups.items()}, state,
+                                       {n: getattr(self, n) for n in props if n not in groups},
+                                       max_grad=max_grad, min_opacity=min_opacity, extent=extent, percent_dense=self.config.percent_dense,
+                                       enable_size_pruning=enable_size_pruning, use_abs_gradient=bool(self.config.use_gof_abs_gradient))
+            for n, g in groups.items():   # _densification_postfix / _prune_points: a new Parameter per group, its state moved to it
+                old = g["params"][0]
+                new = torch.nn.Parameter(res.tensors[n].requires_grad_(True))
+                if state[n] is not None:
+                    stored = self.optimizer.state[old]
+                    stored["exp_avg"], stored["exp_avg_sq"] = res.adam_state[n]
+                    del self.optimizer.state[old]
+                    self.optimizer.state[new] = stored
+                g["params"][0] = new
+                self.register_parameter(n, new)
+            for n, t in res.stats.items():
+                self.register_buffer(n, t.view(-1, *getattr(self, n).shape[1:]))
+            return res.counts
+        swap(GM, "densify_and_prune", densify_and_prune)
+
+        def reset_opacity(self):
+            assert self.optimizer is not None, "Not set up for training"
+            for group in self.optimizer.param_groups:
+                if group.get("name") == "opacities":
+                    old = group["params"][0]
+                    stored = self.optimizer.state.get(old, None)
+                    have = stored is not None and "exp_avg" in stored
+                    new = FG.reset_opacity(old, self.scales, self.filter_3D, stored["exp_avg"] if have else None,
+                                           stored["exp_avg_sq"] if have else None)
+                    if stored is not None:
+                        del self.optimizer.state[old]
+                    group["params"][0] = torch.nn.Parameter(new.requires_grad_(True))
+                    self.register_parameter("opacities", group["params"][0])
+                    if stored is not None:
+                        self.optimizer.state[group["params"][0]] = stored
+        swap(GM, "reset_opacity", reset_opacity)
 
     if edited_module is not None:
         edited = edited_module
