@@ -38,7 +38,8 @@ SOURCES = {
     "preprocess_bwd.hip": ["-fno-slp-vectorize"],
     "api.hip": [],
     "knn.hip": ["-ffp-contract=off"],  # simple_knn.distCUDA2 replacement (include/wg_knn.h)
-    "ssim.hip": [],                    # fused SSIM map fwd/bwd (include/wg_ssim.h)
+    "ssim.hip": [],                    # fused SSIM map fwd/bwd (include/wg_ssim.h) and the forward-only msssim / ssim_down of
+                                       # the uncertainty path (include/wg_msssim.h)
     "activations.hip": ["-ffp-contract=off"],   # fused activations + 3-D filter fwd/bwd (include/wg_activations.h); same flags as
                                                # preprocess.hip, whose raw-parameter mode runs the same device functions (wg_act.h): same bits
     "densify.hip": [],                 # fused densification statistics (include/wg_densify.h) and the fused densify-and-prune
@@ -48,7 +49,7 @@ SOURCES = {
 }
 HEADERS = ["wg_common.h", "wg_alpha.h", "wg_sort.h", "wg_act.h", os.path.join(INCLUDE, "wg_rasterizer.h"), os.path.join(INCLUDE, "wg_knn.h"),
            os.path.join(INCLUDE, "wg_ssim.h"), os.path.join(INCLUDE, "wg_activations.h"), os.path.join(INCLUDE, "wg_densify.h"), os.path.join(INCLUDE, "wg_adam.h"), os.path.join(INCLUDE, "wg_sh_eval.h"),
-           os.path.join(INCLUDE, "wg_filter3d.h"), os.path.join(INCLUDE, "wg_densify_prune.h")]
+           os.path.join(INCLUDE, "wg_filter3d.h"), os.path.join(INCLUDE, "wg_densify_prune.h"), os.path.join(INCLUDE, "wg_msssim.h")]
 
 
 def _newer(target: str, deps) -> bool:

@@ -7,10 +7,15 @@
 One HIP kernel computes the five 11x11 Gaussian-window statistics, the SSIM map and the three partial-derivative maps the
 backward needs; one more kernel is the whole backward (include/wg_ssim.h, csrc/ssim.hip).  Gradients flow to `img1` only:
 `img2` is the ground truth in the reference's use.  There is no CPU fallback: tensors must be float32 on a HIP device.
+
+    from wg_fused_ssim import msssim, ssim_down    # the uncertainty model's two metrics (method.py:126-187), forward only
+    m = msssim(gt, prediction, max_size=400, min_size=80)    # [B, H, W] in levels + 3 launches (include/wg_msssim.h, csrc/ssim.hip)
+    s = ssim_down(gt, prediction, max_size=400)              # [B, H, W] in 3 launches
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -29,6 +34,16 @@ _lib.wg_l1_ssim_loss_forward.restype = _i
 _lib.wg_l1_ssim_loss_forward.argtypes = [_i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]
 _lib.wg_l1_ssim_loss_backward.restype = _i
 _lib.wg_l1_ssim_loss_backward.argtypes = [_i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+_lib.wg_msssim_levels.restype = _i
+_lib.wg_msssim_levels.argtypes = [_i, _i, _i]
+_lib.wg_msssim_scratch_floats.restype = C.c_size_t
+_lib.wg_msssim_scratch_floats.argtypes = [_i] * 7
+_lib.wg_msssim_forward.restype = _i
+_lib.wg_msssim_forward.argtypes = [_i] * 9 + [_vp] * 5
+_lib.wg_ssim_down_scratch_floats.restype = C.c_size_t
+_lib.wg_ssim_down_scratch_floats.argtypes = [_i] * 4
+_lib.wg_ssim_down_forward.restype = _i
+_lib.wg_ssim_down_forward.argtypes = [_i] * 7 + [_vp] * 5
 
 
 def _check(img):
@@ -162,3 +177,87 @@ def l1_ssim_loss(img_l1: torch.Tensor, img_ssim: torch.Tensor, gt: torch.Tensor,
     (l1_mean, ssim_mean) the reference logs (method.py:1970-1972)."""
     loss, parts = _L1SSIMLoss.apply(img_l1, img_ssim, gt, lambda_dssim, loss_mult)
     return (loss, parts[0], parts[1]) if return_parts else loss
+
+
+def _area_size(H: int, W: int, scale_factor: float):
+    """The output size of F.interpolate(scale_factor=..., mode='area'): floor(size * scale) in Python doubles."""
+    return int(math.floor(float(H * scale_factor))), int(math.floor(float(W * scale_factor)))
+
+
+def msssim_plan(H: int, W: int, max_size=None, min_size: int = 200) -> list:
+    """The (h, w) of every pyramid level of msssim(x, y, max_size, min_size) for H x W images (method.py:171-183), level 0 first.
+    Pure host arithmetic: the area resize's floor(size * scale) in Python doubles, then avg_pool2d(2) while both sides exceed min_size."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or min_size < 1:
+        raise ValueError("msssim_plan: H, W and min_size must be positive")
+    h, w = H, W
+    if max_size is not None:
+        h, w = _area_size(H, W, min(1, max(max_size / H, max_size / W)))
+        if h < 1 or w < 1:
+            raise ValueError(f"msssim_plan: max_size={max_size} resizes {H}x{W} to an empty image")
+    levels = [(h, w)]
+    while h > min_size and w > min_size:
+        h, w = h // 2, w // 2
+        levels.append((h, w))
+    return levels
+
+
+def _metric_inputs(name, x, y):
+    for t in (x, y):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32:
+            raise RuntimeError(f"wg_fused_ssim.{name}: float32 tensors on a HIP device are required (there is no CPU path)")
+        if t.requires_grad:
+            raise RuntimeError(f"wg_fused_ssim.{name} is forward-only (the reference calls it on detached images); detach the inputs")
+    if x.shape != y.shape or x.dim() not in (3, 4):
+        raise RuntimeError(f"wg_fused_ssim.{name}: two [B, C, H, W] or [C, H, W] images of the same shape are expected")
+    if x.device != y.device:
+        raise RuntimeError(f"wg_fused_ssim.{name}: both images must be on the same device")
+    batched = x.dim() == 4
+    a, b = x.contiguous(), y.contiguous()
+    if not batched:
+        a, b = a[None], b[None]
+    return a, b, batched
+
+
+def msssim(x: torch.Tensor, y: torch.Tensor, max_size=None, min_size: int = 200) -> torch.Tensor:
+    """method.py:171-187, forward only: [B, C, H, W] -> [B, H, W] (also [C, H, W] -> [H, W]).  One launch per pyramid level plus the
+    resize, the combine and the finish kernel (csrc/ssim.hip); bit-reproducible."""
+    a, b, batched = _metric_inputs("msssim", x, y)
+    B, Cn, H, W = a.shape
+    h0, w0 = msssim_plan(H, W, max_size, min_size)[0]
+    resize = (h0, w0) != (H, W)   # an area resize to the same size is the identity: its launch is skipped
+    final_upsample = max_size is not None
+    dev = a.device
+    n = _lib.wg_msssim_scratch_floats(B, Cn, H, W, h0, w0, int(min_size))
+    if n == 0:
+        raise RuntimeError(f"wg_fused_ssim.msssim: unsupported sizes (B*C={B * Cn}, {H}x{W} -> {h0}x{w0}, min_size={min_size})")
+    scratch = torch.empty((n,), device=dev, dtype=torch.float32)
+    out = torch.empty((B, H, W), device=dev, dtype=torch.float32)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _native._check(_lib.wg_msssim_forward(B, Cn, H, W, h0, w0, int(resize), int(final_upsample), int(min_size), a.data_ptr(), b.data_ptr(),
+                                              scratch.data_ptr(), out.data_ptr(), stream), "wg_msssim_forward")
+    return out if batched else out[0]
+
+
+def ssim_down(x: torch.Tensor, y: torch.Tensor, max_size=None) -> torch.Tensor:
+    """method.py:126-135, forward only: [B, C, H, W] -> [B, H, W] (also [C, H, W] -> [H, W]).  Area resize (down OR up: there is no
+    min(1, .) here), the product-form SSIM, the channel mean, bilinear upsampling back: three launches."""
+    a, b, batched = _metric_inputs("ssim_down", x, y)
+    B, Cn, H, W = a.shape
+    h0, w0 = H, W
+    if max_size is not None:
+        h0, w0 = _area_size(H, W, max(max_size / H, max_size / W))
+        if h0 < 1 or w0 < 1:
+            raise RuntimeError(f"wg_fused_ssim.ssim_down: max_size={max_size} resizes {H}x{W} to an empty image")
+    dev = a.device
+    n = _lib.wg_ssim_down_scratch_floats(B, Cn, h0, w0)
+    if n == 0:
+        raise RuntimeError(f"wg_fused_ssim.ssim_down: unsupported sizes (B*C={B * Cn}, {H}x{W} -> {h0}x{w0})")
+    scratch = torch.empty((n,), device=dev, dtype=torch.float32)
+    out = torch.empty((B, H, W), device=dev, dtype=torch.float32)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _native._check(_lib.wg_ssim_down_forward(B, Cn, H, W, h0, w0, int(max_size is not None), a.data_ptr(), b.data_ptr(), scratch.data_ptr(),
+                                                 out.data_ptr(), stream), "wg_ssim_down_forward")
+    return out if batched else out[0]

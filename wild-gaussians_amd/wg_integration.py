@@ -28,6 +28,10 @@ needs the few-line edits INTEGRATION.md lists.  What IS swapped, each with the r
                         parameters and buffers are re-registered and `optimizer.state` re-keyed as the reference does (a new nn.Parameter
                         per group, the state moved to it).  `GaussianModel.reset_opacity` (method.py:1249-1278) ->
                         wg_fused_gaussians.reset_opacity.  The split's draw is torch.randn on the device
+  uncertainty_metrics   (OFF by default: results move within float32 rounding, and callers' logged metrics must not move unasked)
+                        `method.msssim` (method.py:171-187) and `method.ssim_down` (:126-135), which UncertaintyModel._compute_losses
+                        looks up as module globals on every step -> wg_fused_ssim.msssim / ssim_down (forward only); calls they do not
+                        cover (CPU tensors, a dtype other than float32, an input that requires grad) go to the original functions
   edited_module         (off by default) `GaussianModel._render_internal` -> the one of a module the INTEGRATOR supplies: a copy of the caller with
                         INTEGRATION.md section 5's "two_colour" or "two_tone" edit applied (the documented diff is the deliverable; this package
                         does not rewrite anybody's source -- tests/real_caller/render_edits.py is the test tool that builds such a module in memory)
@@ -41,7 +45,8 @@ import torch
 
 
 def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True, densification_stats: bool = True, activations: bool = True,
-                 eval_sh: bool = True, geometry_reuse: bool = True, edited_module=None, filter_3d: bool = False, densify: bool = False):
+                 eval_sh: bool = True, geometry_reuse: bool = True, edited_module=None, filter_3d: bool = False, densify: bool = False,
+                 uncertainty_metrics: bool = False):
     """-> a function that restores everything that was replaced.  `model`: an already constructed GaussianModel (e.g.
     `WildGaussians(...).model`) whose existing optimizer should be adopted too.
     edited_module (default None): a module object holding a copy of the caller with INTEGRATION.md section 5's edit of `_render_internal`
@@ -152,6 +157,25 @@ def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True
                     if stored is not None:
                         self.optimizer.state[group["params"][0]] = stored
         swap(GM, "reset_opacity", reset_opacity)
+
+    if uncertainty_metrics:
+        orig_msssim, orig_ssim_down = method_module.msssim, method_module.ssim_down
+
+        def covered(*images):
+            return all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and not t.requires_grad and t.dim() in (3, 4)
+                       for t in images)
+
+        def fused_msssim(x, y, max_size=None, min_size=200):
+            if not covered(x, y):
+                return orig_msssim(x, y, max_size=max_size, min_size=min_size)   # the caller's own code, not a fallback of this library
+            return wg_fused_ssim.msssim(x, y, max_size=max_size, min_size=min_size)
+
+        def fused_ssim_down(x, y, max_size=None):
+            if not covered(x, y):
+                return orig_ssim_down(x, y, max_size=max_size)
+            return wg_fused_ssim.ssim_down(x, y, max_size=max_size)
+        swap(method_module, "msssim", fused_msssim)
+        swap(method_module, "ssim_down", fused_ssim_down)
 
     if edited_module is not None:
         edited = edited_module
