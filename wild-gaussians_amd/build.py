@@ -136,7 +136,7 @@ def build_probes(force: bool = False) -> list:
 
 def build_torch_binding(force: bool = False) -> str:
     """csrc/torch_binding.cpp -> diff_gaussian_rasterization/_C_torch.so: the compiled torch binding of the C-ABI (INTEGRATION.md section 2 as
-    a file; the ctypes binding stays the default).  Host C++ only: g++ against torch's headers, linked to libwg_rasterizer.so next to it
+    a file; the default binding once it is built, the ctypes one otherwise: the end of _C.py decides).  Host C++ only: g++ against torch's headers, linked to libwg_rasterizer.so next to it
     (rpath $ORIGIN)."""
     import sysconfig
     import torch

@@ -87,8 +87,6 @@ struct Mailbox {
     }
 };
 thread_local Mailbox t_mailbox;
-thread_local uint32_t t_last_instances_per_tile = 0;  // density of this thread's previous frame: the near / far split's "try it" hint
-thread_local uint32_t t_split_backoff = 0;            // frames for which the split is not attempted after one that needed the far phase
 // The split's aimed number of near instances per tile, ADAPTED per host thread (option "near_adapt", default on; a fixed "near_per_tile" wins):
 // every split frame reports how many tiles ran out of near instances and the aim it ran with (the mailbox's far_report, read a frame or two
 // late).  Four clean reports at the current aim lower it by 10 %; a frame in which ANY tile asked lifts it to a floor an eighth (a sixteenth for a
@@ -104,7 +102,71 @@ struct NearAdapt {
     int P = 0;
     bool same_scene(int P_) const { return P != 0 && (int64_t)P_ * 2 >= (int64_t)P && (int64_t)P_ <= (int64_t)P * 2; }
 };
-thread_local NearAdapt t_near;
+// What steers the near / far split from frame to frame, per host thread.
+struct SplitState {
+    NearAdapt near;
+    uint32_t backoff = 0;                  // frames for which the split is not attempted after one that needed the far phase
+    uint32_t last_instances_per_tile = 0;  // density of this thread's previous frame: the split's "try it" hint
+    uint32_t next_aim(const wg::Options& opt, int P, int tiles);
+    void forget_scene() { near = NearAdapt(); if (t_mailbox.host) t_mailbox.host->far_report = 0ull; }   // the controller starts afresh, a report still waiting in the thread's mailbox is dropped
+    void reset(bool density_hint) { forget_scene(); backoff = 0; if (density_hint) last_instances_per_tile = 0; }   // wg_set_option("near_adapt") / ("near_split"): only the latter clears the density hint too
+};
+thread_local SplitState t_split;
+// Takes the far report of an earlier split frame out of the thread's mailbox, updates the aim, its floor and the back-off: THIS frame's near instances per tile.
+uint32_t SplitState::next_aim(const wg::Options& opt, int P, int tiles) {
+    // Near / far split of dense frames (binning.hip): attempted from band_list_min_p Gaussians on (or whenever forced), on the LDS
+    // binning path with the lazy sort available; whether it is ACTIVE for this frame is decided on the device (dense enough?) and
+    // comes back with the instance count.
+    // (measured at 10 M Gaussians / 4K, where pixels stop ~220 instances deep: 2050 near instances per tile 300 fps, 1400 324 fps,
+    // 1000 359 fps, none of them sending a tile to the far phase; 1.5 x the front target keeps a margin for deeper walks)
+    //  With the difference-grid counting: 1230 / 1000 / 900 per tile 365 / 404 / 427 fps there, 1021 / 1103 / 1145 train iter/s on
+    //  the dense x3 frame: a near bag that fits the 1024-key network is sorted without a selection pass.)
+    const uint32_t near_default = (opt.lazy.target * 11u) / 10u;
+    const bool near_adaptive = opt.near_per_tile <= 0 && opt.near_adapt != 0 && opt.near_split < 0;
+    if (near_adaptive && !near.same_scene(P)) {
+        forget_scene();   // (with it a report of the other scene's last frame)
+        near.P = P;
+    }
+    if (near_adaptive && (near.cur == 0u || near.cur > near_default)) near.cur = near_default;
+    // Frames whose pixels do not saturate (low opacities: after an opacity reset, early in training) walk their whole lists: every
+    // band then asks for its far instances and the split only adds a second, slower scatter.  The last split frame's request mask
+    // arrives through the mailbox: the number of tiles that asked.  A few deep tiles are what the far phase is for (its cost is a
+    // walk of the flagged bands' far Gaussians); after a frame in which more than 2 % of the tiles asked, the split is not
+    // attempted for the next 64 frames of this thread (automatic mode only).
+    if (opt.near_split < 0) {
+        Mailbox& mb = t_mailbox;
+        unsigned long long report = 0ull;
+        if (mb.host) report = __atomic_exchange_n(&mb.host->far_report, 0ull, __ATOMIC_RELAXED);   // (take it: a report is acted on once)
+        if (report != 0ull) {
+            const uint32_t word = (uint32_t)report - 1u, far_tiles = word & 0xffffffu, far_bands = word >> 24, report_aim = (uint32_t)(report >> 32);
+            // (a frame that failed at an aim the adaptation had LOWERED says the aim was too low, not that the scene does not saturate: the aim is
+            //  lifted below, the split stays on -- with the back-off a single probing step cost 64 unsplit frames: 536 -> 447 fps over 600 frames)
+            if ((uint64_t)far_tiles * 50u > (uint64_t)tiles && !(near_adaptive && report_aim != 0u && report_aim < near_default)) backoff = 64;
+            if (near_adaptive && report_aim != 0u) {
+                near.last_far = far_tiles;
+                // ANY tile that asked is a failure of the aim its frame ran with.  (Rounds of this controller: "more than one tile in a thousand"
+                // let thirty tiles in all eight bands pass as clean while every frame paid the far scatter of every band, 536 -> 447 fps over 600
+                // frames; "at most two bands" still let the aim rest where a few tiles asked in EVERY frame, each paying a far phase: 2.35 instead of
+                // 1.82 ms per frame for 2000 frames at 10 M Gaussians / 4K, profiles/r6/near_trace_*.)  The floor remembers the level, so there is
+                // no saw-tooth: one or two slow frames per probing step, and a probing step only when the floor has decayed (every 2048 frames).
+                if (far_tiles != 0u) {
+                    // the floor goes an eighth above the aim THE FAILING FRAME ran with (the report carries it) -- a sixteenth when only a handful of
+                    // tiles asked (the aim sits right at the deepest tiles' need): reports lag a frame or two behind the calls when the caller does not
+                    // synchronise, and two frames issued at one failing aim used to lift the floor twice (386 failed -> 435 -> 490 where 435 sufficed)
+                    const uint32_t step = ((uint64_t)far_tiles * 1000u > (uint64_t)tiles || far_bands > 2u) ? report_aim / 8u : report_aim / 16u;
+                    near.floor = std::min(near_default, std::max(near.floor, report_aim + step + 1u));
+                    near.cur = std::max(near.cur, near.floor);
+                    near.clean = 0;
+                } else if (report_aim == near.cur && ++near.clean >= 4u) {   // (four clean frames AT the current aim)
+                    near.clean = 0;
+                    near.cur = std::max(std::max(near.floor, 192u), (near.cur * 9u) / 10u);
+                }
+                if (++near.age >= 2048u) { near.age = 0; near.floor = (near.floor * 19u) / 20u; }
+            }
+        }
+    }
+    return opt.near_per_tile > 0 ? (uint32_t)opt.near_per_tile : (near_adaptive ? near.cur : near_default);
+}
 
 // Speculative forward: what this host thread's recent frames looked like.  A prediction is made only from frames of the same image
 // size and a similar number of Gaussians (training: the model grows slowly, the cameras alternate -- hence the maximum over the last
@@ -302,7 +364,7 @@ int settle_deferred() {
         if (!ok) return hip_fail(hipErrorUnknown, "deferred forward: the instance count never arrived");
     }
     t_spec.push(t_deferred.P, t_deferred.W, t_deferred.H, st.num_rendered, st.max_tile_count);
-    t_last_instances_per_tile = st.num_rendered / (uint32_t)std::max(1, ((t_deferred.W + wg::TILE_X - 1) / wg::TILE_X) * ((t_deferred.H + wg::TILE_Y - 1) / wg::TILE_Y));
+    t_split.last_instances_per_tile = st.num_rendered / (uint32_t)std::max(1, ((t_deferred.W + wg::TILE_X - 1) / wg::TILE_X) * ((t_deferred.H + wg::TILE_Y - 1) / wg::TILE_Y));
     t_wait.spec_frames += 1;
     // The owning thread has the verdict now: the frame's ticket gives its address up (a frame that is never differentiated -- evaluation,
     // no_grad -- would otherwise leave it there for whatever frame the caller's allocator hands the same address to next).
@@ -657,172 +719,93 @@ int wg_forward_status(char* image_buffer, int width, int height, int* num_render
     return WG_OK;
 }
 
-static int forward_impl(const wg_forward_args& a) {
-    // (the body below reads the arguments under the reference interface's names)
-    const wg_alloc_fn geometry_alloc = a.geometry_alloc, binning_alloc = a.binning_alloc, image_alloc = a.image_alloc;
-    void* const geometry_user = a.geometry_user; void* const binning_user = a.binning_user; void* const image_user = a.image_user;
-    const int P = a.P, D = a.D, M = a.M, width = a.width, height = a.height, prefiltered = a.prefiltered;
-    const float scale_modifier = a.scale_modifier, tan_fovx = a.tan_fovx, tan_fovy = a.tan_fovy, kernel_size = a.kernel_size;
-    const float *background = a.background, *means3D = a.means3D, *shs = a.shs, *colors_precomp = a.colors_precomp, *opacities = a.opacities,
-                *scales = a.scales, *rotations = a.rotations, *cov3D_precomp = a.cov3D_precomp, *viewmatrix = a.viewmatrix,
-                *projmatrix = a.projmatrix, *cam_pos = a.cam_pos, *subpixel_offset = a.subpixel_offset;
-    float* const out_color = a.out_color;
-    int* const radii = a.radii;
-    void* const stream_ = a.stream;
-    const wg_sh_tone *tone = a.tone, *tone2 = a.tone2;
-    const wg_second_image* second = a.second;
-    const wg_raw_gaussians* raw = a.raw;
-    const bool sh_second = a.sh_second != 0;
-    const int fixed_capacity = a.binning_capacity;
-    if (fixed_capacity < 0 || (fixed_capacity > 0 && a.debug)) return WG_ERR_INVALID_ARGUMENT;
-    const int debug = fixed_capacity > 0 ? 0 : a.debug;
-    if (a.recolor != nullptr) return WG_ERR_INVALID_ARGUMENT;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+// The result-affecting switches are the CALL's (wg_call_options), never the process's: the process's options with the call's three on top.
+static wg::Options call_options_snapshot(const wg_call_options* call) {
     wg::Options opt = options_snapshot();
-    {   // the result-affecting switches are the CALL's (wg_call_options), never the process's
-        const wg_call_options dflt = WG_CALL_OPTIONS_DEFAULT;
-        const wg_call_options& co = a.options ? *a.options : dflt;
-        opt.exact_compositing = co.exact_compositing != 0; opt.deterministic_backward = co.deterministic_backward != 0; opt.grad_record = co.grad_record != 0;
-    }
+    const wg_call_options dflt = WG_CALL_OPTIONS_DEFAULT;
+    const wg_call_options& co = call ? *call : dflt;
+    opt.exact_compositing = co.exact_compositing != 0; opt.deterministic_backward = co.deterministic_backward != 0; opt.grad_record = co.grad_record != 0;
+    return opt;
+}
+
+// Every check of a forward call, in the order callers depend on (a call that trips two returns what the first says); the previous frame's deferred verdict is taken in between.
+static int check_forward_args(const wg_forward_args& a, const wg::Options& opt) {
+    const int P = a.P;
+    const bool sh_second = a.sh_second != 0;
+    if (a.binning_capacity < 0 || (a.binning_capacity > 0 && a.debug)) return WG_ERR_INVALID_ARGUMENT;
+    if (a.recolor != nullptr) return WG_ERR_INVALID_ARGUMENT;
     // two colour sets over one walk: a second set of precomputed colours (wg_second_image), or the SAME SH coefficients through a
     // second tone (sh_second; wg_forward_args::sh_second).  The second image is required either way.
-    float* out_color2 = nullptr;
-    if (second != nullptr) {   // (the second image is written whatever P is: the background alone when there is nothing to composite)
-        if (!second->out_color2) return WG_ERR_INVALID_ARGUMENT;
-        if (P > 0 && !sh_second && (!second->colors_precomp2 || shs != nullptr || !colors_precomp)) return WG_ERR_INVALID_ARGUMENT;
-        if (P > 0 && sh_second && (second->colors_precomp2 || shs == nullptr || colors_precomp)) return WG_ERR_INVALID_ARGUMENT;
-        out_color2 = second->out_color2;
+    if (a.second != nullptr) {   // (the second image is written whatever P is: the background alone when there is nothing to composite)
+        if (!a.second->out_color2) return WG_ERR_INVALID_ARGUMENT;
+        if (P > 0 && !sh_second && (!a.second->colors_precomp2 || a.shs != nullptr || !a.colors_precomp)) return WG_ERR_INVALID_ARGUMENT;
+        if (P > 0 && sh_second && (a.second->colors_precomp2 || a.shs == nullptr || a.colors_precomp)) return WG_ERR_INVALID_ARGUMENT;
     } else if (sh_second) {
         return WG_ERR_INVALID_ARGUMENT;
     }
     // get_gaussians() inside the preprocess kernel (wg_raw_gaussians): needs the scale / rotation pair it acts on
-    if (raw != nullptr && P > 0 && (!raw->filter_3D || !scales || !rotations || cov3D_precomp)) return WG_ERR_INVALID_ARGUMENT;
-    const bool fixed = fixed_capacity > 0;  // no host rendezvous at all: the caller's capacity, the superset (lazy) flow, a device-side verdict
-    {
-        const int settled = settle_deferred();
-        if (settled != WG_OK) return settled;
-    }
-    if (tone != nullptr && shs == nullptr && P > 0) return WG_ERR_INVALID_ARGUMENT;  // the tone acts on SH coefficients
-    if (!geometry_alloc || !binning_alloc || !image_alloc) return WG_ERR_INVALID_ARGUMENT;
-    if (P < 0 || width <= 0 || height <= 0 || D < 0 || D > 3) return WG_ERR_INVALID_ARGUMENT;
-    if (!background || !out_color || !viewmatrix || !projmatrix) return WG_ERR_INVALID_ARGUMENT;  // subpixel_offset may be null (= zeros)
+    if (a.raw != nullptr && P > 0 && (!a.raw->filter_3D || !a.scales || !a.rotations || a.cov3D_precomp)) return WG_ERR_INVALID_ARGUMENT;
+    if (const int settled = settle_deferred(); settled != WG_OK) return settled;
+    if (a.tone != nullptr && a.shs == nullptr && P > 0) return WG_ERR_INVALID_ARGUMENT;  // the tone acts on SH coefficients
+    if (!a.geometry_alloc || !a.binning_alloc || !a.image_alloc) return WG_ERR_INVALID_ARGUMENT;
+    if (P < 0 || a.width <= 0 || a.height <= 0 || a.D < 0 || a.D > 3) return WG_ERR_INVALID_ARGUMENT;
+    if (!a.background || !a.out_color || !a.viewmatrix || !a.projmatrix) return WG_ERR_INVALID_ARGUMENT;  // subpixel_offset may be null (= zeros)
     if (P > 0) {
-        if (!means3D || !opacities) return WG_ERR_INVALID_ARGUMENT;
+        if (!a.means3D || !a.opacities) return WG_ERR_INVALID_ARGUMENT;
         // exactly one colour source / one covariance source (GaussianRasterizer.forward, __init__.py:212-216)
-        if ((shs == nullptr) == (colors_precomp == nullptr)) return WG_ERR_INVALID_ARGUMENT;
-        if (cov3D_precomp == nullptr && (!scales || !rotations)) return WG_ERR_INVALID_ARGUMENT;
-        if (shs != nullptr && (!cam_pos || M < (D + 1) * (D + 1))) return WG_ERR_INVALID_ARGUMENT;
+        if ((a.shs == nullptr) == (a.colors_precomp == nullptr)) return WG_ERR_INVALID_ARGUMENT;
+        if (a.cov3D_precomp == nullptr && (!a.scales || !a.rotations)) return WG_ERR_INVALID_ARGUMENT;
+        if (a.shs != nullptr && (!a.cam_pos || a.M < (a.D + 1) * (a.D + 1))) return WG_ERR_INVALID_ARGUMENT;
     }
+    const int tiles = ((a.width + wg::TILE_X - 1) / wg::TILE_X) * ((a.height + wg::TILE_Y - 1) / wg::TILE_Y);
+    if (a.binning_capacity > 0 && (tiles > wg::BIN_MAX_TILES || opt.force_global_sort || !opt.lazy.enabled)) return WG_ERR_INVALID_ARGUMENT;  // LDS binning + lazy sort only
+    return WG_OK;
+}
 
-    const int gx = (width + wg::TILE_X - 1) / wg::TILE_X, gy = (height + wg::TILE_Y - 1) / wg::TILE_Y;
-    const int tiles = gx * gy;
-
-    if (fixed && (tiles > wg::BIN_MAX_TILES || opt.force_global_sort || !opt.lazy.enabled)) return WG_ERR_INVALID_ARGUMENT;  // LDS binning + lazy sort only
-    const bool band_lists = (size_t)P >= (size_t)opt.band_list_min_p;  // size and carving from the same snapshot
-    char* geom_chunk = geometry_alloc(required_bytes([&](char*& c) { wg::GeometryState::fromChunk(c, (size_t)P, band_lists); }), geometry_user);
-    char* img_chunk = image_alloc(wg_image_buffer_size(width, height), image_user);
-    if (!geom_chunk || !img_chunk) return WG_ERR_ALLOC;
-    remember_mode(img_chunk, opt.exact_compositing ? 1 : 0);
-    wg::GeometryState geom = wg::GeometryState::fromChunk(geom_chunk, (size_t)P, band_lists);
-    wg::ImageState img = wg::ImageState::fromChunk(img_chunk, (size_t)width * height, (size_t)tiles);
-
+static wg::FwdParams forward_params(const wg_forward_args& a, const wg::Options& opt, int gx, int gy) {
+    const int P = a.P;
     wg::FwdParams fp;
-    fp.P = P; fp.D = D; fp.M = M; fp.W = width; fp.H = height; fp.gx = gx; fp.gy = gy;
-    fp.means3D = means3D; fp.shs = shs; fp.colors_precomp = colors_precomp; fp.opacities = opacities;
-    fp.colors_precomp2 = (out_color2 && P > 0 && !sh_second) ? second->colors_precomp2 : nullptr;
-    if (raw != nullptr && P > 0) fp.filter_3D = raw->filter_3D;
+    fp.P = P; fp.D = a.D; fp.M = a.M; fp.W = a.width; fp.H = a.height; fp.gx = gx; fp.gy = gy;
+    fp.means3D = a.means3D; fp.shs = a.shs; fp.colors_precomp = a.colors_precomp; fp.opacities = a.opacities;
+    fp.colors_precomp2 = (a.second != nullptr && P > 0 && !a.sh_second) ? a.second->colors_precomp2 : nullptr;
+    if (a.raw != nullptr && P > 0) fp.filter_3D = a.raw->filter_3D;
     fp.nt_stream = opt.sh_stream == 1 || (opt.sh_stream < 0 && P <= opt.sh_stream_max_p);
-    fp.scales = scales; fp.scale_modifier = scale_modifier; fp.rotations = rotations; fp.cov3D_precomp = cov3D_precomp;
-    fp.viewmatrix = viewmatrix; fp.projmatrix = projmatrix; fp.cam_pos = cam_pos;
-    fp.tan_fovx = tan_fovx; fp.tan_fovy = tan_fovy;
-    fp.focal_y = height / (2.0f * tan_fovy);  // rasterizer_impl.cu:224-225
-    fp.focal_x = width / (2.0f * tan_fovx);
-    fp.kernel_size = kernel_size; fp.prefiltered = prefiltered;
+    fp.scales = a.scales; fp.scale_modifier = a.scale_modifier; fp.rotations = a.rotations; fp.cov3D_precomp = a.cov3D_precomp;
+    fp.viewmatrix = a.viewmatrix; fp.projmatrix = a.projmatrix; fp.cam_pos = a.cam_pos;
+    fp.tan_fovx = a.tan_fovx; fp.tan_fovy = a.tan_fovy;
+    fp.focal_y = a.height / (2.0f * a.tan_fovy);  // rasterizer_impl.cu:224-225
+    fp.focal_x = a.width / (2.0f * a.tan_fovx);
+    fp.kernel_size = a.kernel_size; fp.prefiltered = a.prefiltered;
+    return fp;
+}
 
-    int num_rendered = 0;
-    uint32_t max_tile_count = 0;
-    bool huge_frame = false;
+// One forward call's frame, built once by forward_impl after the checks: what its steps share, and the steps themselves.
+struct ForwardFrame {
+    const wg_forward_args& a;
+    const wg::Options& opt;
+    const int P = a.P, width = a.width, height = a.height, gx = (width + wg::TILE_X - 1) / wg::TILE_X, gy = (height + wg::TILE_Y - 1) / wg::TILE_Y, tiles = gx * gy, debug = a.debug;
+    const hipStream_t stream = reinterpret_cast<hipStream_t>(a.stream);
+    const bool fixed = a.binning_capacity > 0;                     // no host rendezvous at all: the caller's capacity, the superset (lazy) flow, a device-side verdict
+    const bool huge_frame = P > 0 && tiles > wg::BIN_MAX_TILES;    // tile histogram does not fit LDS: count through the per-Gaussian prefix sum instead
+    float* const out_color2 = a.second ? a.second->out_color2 : nullptr;
+    wg::GeometryState geom{};
+    wg::ImageState img{};
+    wg::FwdParams fp{};
+    uint32_t* order_table = nullptr;
+    uint32_t order_slots = 0, near_per_tile = 0;
+    bool try_split = false, lazy_colour = false;
     Mailbox* mbox = nullptr;
-    uint32_t order_slots = 0;
-    uint32_t* const order_table = (P > 0 && !debug) ? order_table_for(opt, tiles, stream, &order_slots) : nullptr;
-    // Near / far split of dense frames (binning.hip): attempted from band_list_min_p Gaussians on (or whenever forced), on the LDS
-    // binning path with the lazy sort available; whether it is ACTIVE for this frame is decided on the device (dense enough?) and
-    // comes back with the instance count.
-    // (measured at 10 M Gaussians / 4K, where pixels stop ~220 instances deep: 2050 near instances per tile 300 fps, 1400 324 fps,
-    // 1000 359 fps, none of them sending a tile to the far phase; 1.5 x the front target keeps a margin for deeper walks)
-    //  With the difference-grid counting: 1230 / 1000 / 900 per tile 365 / 404 / 427 fps there, 1021 / 1103 / 1145 train iter/s on
-    //  the dense x3 frame: a near bag that fits the 1024-key network is sorted without a selection pass.)
-    const uint32_t near_default = (opt.lazy.target * 11u) / 10u;
-    const bool near_adaptive = opt.near_per_tile <= 0 && opt.near_adapt != 0 && opt.near_split < 0;
-    if (near_adaptive && !t_near.same_scene(P)) {
-        t_near = NearAdapt();
-        t_near.P = P;
-        if (t_mailbox.host) t_mailbox.host->far_report = 0ull;   // (a report of the other scene's last frame)
-    }
-    if (near_adaptive && (t_near.cur == 0u || t_near.cur > near_default)) t_near.cur = near_default;
-    // Frames whose pixels do not saturate (low opacities: after an opacity reset, early in training) walk their whole lists: every
-    // band then asks for its far instances and the split only adds a second, slower scatter.  The last split frame's request mask
-    // arrives through the mailbox: the number of tiles that asked.  A few deep tiles are what the far phase is for (its cost is a
-    // walk of the flagged bands' far Gaussians); after a frame in which more than 2 % of the tiles asked, the split is not
-    // attempted for the next 64 frames of this thread (automatic mode only).
-    if (opt.near_split < 0) {
-        Mailbox& mb = t_mailbox;
-        unsigned long long report = 0ull;
-        if (mb.host) report = __atomic_exchange_n(&mb.host->far_report, 0ull, __ATOMIC_RELAXED);   // (take it: a report is acted on once)
-        if (report != 0ull) {
-            const uint32_t word = (uint32_t)report - 1u, far_tiles = word & 0xffffffu, far_bands = word >> 24, report_aim = (uint32_t)(report >> 32);
-            // (a frame that failed at an aim the adaptation had LOWERED says the aim was too low, not that the scene does not saturate: the aim is
-            //  lifted below, the split stays on -- with the back-off a single probing step cost 64 unsplit frames: 536 -> 447 fps over 600 frames)
-            if ((uint64_t)far_tiles * 50u > (uint64_t)tiles && !(near_adaptive && report_aim != 0u && report_aim < near_default)) t_split_backoff = 64;
-            if (near_adaptive && report_aim != 0u) {
-                t_near.last_far = far_tiles;
-                // ANY tile that asked is a failure of the aim its frame ran with.  (Rounds of this controller: "more than one tile in a thousand"
-                // let thirty tiles in all eight bands pass as clean while every frame paid the far scatter of every band, 536 -> 447 fps over 600
-                // frames; "at most two bands" still let the aim rest where a few tiles asked in EVERY frame, each paying a far phase: 2.35 instead of
-                // 1.82 ms per frame for 2000 frames at 10 M Gaussians / 4K, profiles/r6/near_trace_*.)  The floor remembers the level, so there is
-                // no saw-tooth: one or two slow frames per probing step, and a probing step only when the floor has decayed (every 2048 frames).
-                if (far_tiles != 0u) {
-                    // the floor goes an eighth above the aim THE FAILING FRAME ran with (the report carries it) -- a sixteenth when only a handful of
-                    // tiles asked (the aim sits right at the deepest tiles' need): reports lag a frame or two behind the calls when the caller does not
-                    // synchronise, and two frames issued at one failing aim used to lift the floor twice (386 failed -> 435 -> 490 where 435 sufficed)
-                    const uint32_t step = ((uint64_t)far_tiles * 1000u > (uint64_t)tiles || far_bands > 2u) ? report_aim / 8u : report_aim / 16u;
-                    t_near.floor = std::min(near_default, std::max(t_near.floor, report_aim + step + 1u));
-                    t_near.cur = std::max(t_near.cur, t_near.floor);
-                    t_near.clean = 0;
-                } else if (report_aim == t_near.cur && ++t_near.clean >= 4u) {   // (four clean frames AT the current aim)
-                    t_near.clean = 0;
-                    t_near.cur = std::max(std::max(t_near.floor, 192u), (t_near.cur * 9u) / 10u);
-                }
-                if (++t_near.age >= 2048u) { t_near.age = 0; t_near.floor = (t_near.floor * 19u) / 20u; }
-            }
-        }
-    }
-    const uint32_t near_per_tile = opt.near_per_tile > 0 ? (uint32_t)opt.near_per_tile : (near_adaptive ? t_near.cur : near_default);
-    const bool backoff = opt.near_split < 0 && t_split_backoff > 0;
-    if (backoff) t_split_backoff--;
-    // Automatic mode attempts it for large scenes and whenever this host thread's previous frame was dense (a performance hint only:
-    // the threshold pass costs ~15 us, the results are the same either way).
-    const bool try_split = P > 0 && tiles <= wg::BIN_MAX_TILES && opt.lazy.enabled && !opt.force_global_sort && opt.near_split != 0 &&
-                           wg::GeometryState::band_lists_possible((size_t)P) &&
-                           (opt.near_split == 1 || P >= opt.band_list_min_p || t_last_instances_per_tile >= wg::SPLIT_DENSE_AVG) && !backoff;
-    bool split_active = false;
-    // Frames that attempt the split with plain SH colours colour their Gaussians LAZILY: the per-Gaussian kernel leaves the colour out (and the
-    // 192-byte SH block unread), the near Gaussians are coloured once the threshold is known, the far ones only if a tile asks for its far
-    // instances (preprocess.hip: GEOM_ONLY, sh_colour_kernel).  Same colours, bit for bit, for every Gaussian the walk can reach.
-    const bool lazy_colour = try_split && opt.lazy_colour != 0 && P >= opt.lazy_colour_min_p && shs != nullptr && colors_precomp == nullptr && tone == nullptr && tone2 == nullptr &&
-                             !sh_second && out_color2 == nullptr && raw == nullptr;   // (plain SH colours of activated parameters: the combinations the suite holds)
-
     // ---- what depends on the instance count, as functions of it (used by the speculative and by the classic flow alike) ----
     // Longest per-tile list decides the binning path: full register sort of every tile, lazy front sort when lists are long,
     // global radix sort (the reference's scheme) when forced, when the frame is too large for the LDS histogram, or when a
     // list exceeds the register sort and the lazy sort is switched off.
     // (an active split implies the lazy path: its buckets only hold the near instances at first)
-    auto lazy_for = [&](bool split_on, uint32_t longest) {
+    bool lazy_for(bool split_on, uint32_t longest) const {
         return split_on || (opt.lazy.enabled && !opt.force_global_sort && !huge_frame && longest > opt.lazy.min_len + opt.lazy.min_len / 4);
-    };
+    }
     // lazy sort: bucket entries carry a coarse depth code above the id for the front extraction, as wide as the ids allow
     // (2^20 Gaussians or fewer: 12 bits; up to 2^24: 8 bits; more: none)
-    auto code_bits_for = [&](bool lazy) {
+    int code_bits_for(bool lazy) const {
         int code_bits = 0;
         if (lazy && opt.depth_codes && P <= (1 << 24)) {
             int id_bits = 20;
@@ -831,197 +814,235 @@ static int forward_impl(const wg_forward_args& a) {
             if (opt.depth_codes >= 8 && opt.depth_codes <= code_bits) code_bits = opt.depth_codes;  // a narrower code than the ids allow
         }
         return code_bits;
-    };
-    // Everything behind the count on the LDS binning path: scatter -> per-tile sort (full, or lazy front) -> render -> [fix-up ->
-    // far scatter -> fix-up].  R sizes the scatter's staging passes only; `longest` picks the sort network; `far` = the split may be
-    // active (its two extra launches return at once when it is not, or when no tile asked); guard = the frame's BinStats when the
-    // kernels are enqueued BEFORE the count is known (speculation), nullptr otherwise.
-    auto enqueue_tail = [&](const wg::BinningState& bin, uint32_t R, uint32_t longest, bool lazy, bool far, const wg::BinStats* guard) -> int {
-        const int code_bits = code_bits_for(lazy);
-        uint32_t emit = R;  // what the scatter will emit, for the sizing of its staging passes: everything, or about near_per_tile per tile
-        if (far) emit = (uint32_t)std::min<uint64_t>(emit, (uint64_t)near_per_tile * (uint64_t)tiles * 5u / 4u);
-        WG_STAGE(WG_STAGE_DUPLICATE_KEYS, wg::launch_tile_scatter(P, geom, img, bin, gx, tiles, emit, code_bits, opt.staged_scatter, opt.staged_cap, try_split, guard, stream), "tile_scatter");
-        if (lazy) WG_STAGE(WG_STAGE_SORT, wg::launch_tile_sort_lazy(img, bin, geom, tiles, code_bits, opt.lazy, try_split, guard, stream), "tile_sort_lazy");
-        else WG_STAGE(WG_STAGE_SORT, wg::launch_tile_sort(img, bin, geom, tiles, longest, guard, stream), "tile_sort");
-        WG_STAGE(WG_STAGE_RENDER_FORWARD,
-                 wg::launch_render_forward(width, height, gx, gy, img, bin, geom, subpixel_offset, background, out_color, out_color2, lazy, opt.exact_compositing != 0, guard, order_table, order_slots, ORDER_STRIDE, stream),
-                 "render_forward");
-        if (lazy) {
-            WG_STAGE(WG_STAGE_RENDER_FIXUP,
-                     wg::launch_render_fixup(code_bits, width, height, gx, gy, img, bin, geom, subpixel_offset, background, out_color, out_color2, opt.lazy, try_split, 0, opt.exact_compositing != 0, (wg::HostMailbox*)nullptr, guard, stream),
-                     "render_fixup");
-            if (far) {  // all return at once unless some tile ran out of near instances with pixels still accumulating
-                if (lazy_colour) WG_STAGE(WG_STAGE_PREPROCESS, wg::launch_sh_colour(fp, geom, img.split, true, stream), "sh_colour_far");
-                WG_STAGE(WG_STAGE_DUPLICATE_KEYS, wg::launch_tile_scatter_far(P, geom, img, bin, gx, tiles, code_bits, guard, stream), "tile_scatter_far");
-                WG_STAGE(WG_STAGE_RENDER_FIXUP,
-                         wg::launch_render_fixup(code_bits, width, height, gx, gy, img, bin, geom, subpixel_offset, background, out_color, out_color2, opt.lazy, true, 1, opt.exact_compositing != 0, mbox ? mbox->dev : (wg::HostMailbox*)nullptr, guard, stream),
-                         "render_fixup_far");
-            }
-        }
-        return WG_OK;
-    };
+    }
+    int preprocess_and_count(wg::FwdOrderArgs& fo) const;
+    int scan_and_speculate(const wg::FwdOrderArgs& fo, wg::SpecLimits& spec);
+    int enqueue_tail(const wg::BinningState& bin, uint32_t R, uint32_t longest, bool lazy, bool far, const wg::BinStats* guard) const;
+    int rendezvous(wg::BinStats& st) const;
+    int global_sort_tail(const wg::BinningState& bin, int num_rendered) const;
+};
 
-    bool rendered = false;  // the render kernels of this frame are already in the stream (a speculation that held)
-    if (P > 0) {
-        if (!order_table) {   // (what wg_view_image's order_key says then: no row)
-            hipError_t e0 = hipMemsetAsync(img.order_key, 0xff, sizeof(uint32_t), stream);
-            if (e0 != hipSuccess) return hip_fail(e0, "order_key memset");
-        }
-        wg::FwdOrderArgs fo;   // the forward render kernel's launch order: eight workgroups riding along in the tile scan's launch
-        if (order_table) {
-            fo.viewmatrix = viewmatrix; fo.projmatrix = projmatrix; fo.W = width; fo.H = height; fo.table = order_table; fo.slots = order_slots;
-            fo.stride = ORDER_STRIDE; fo.order = img.order_fwd; fo.key_out = img.order_key; fo.period = (uint32_t)std::max(opt.order_period, 0);
-            if (tiles > wg::BIN_MAX_TILES || opt.fused_scan) {   // no stand-alone tile scan on these paths: a launch of its own, first in the stream
-                WG_STAGE(WG_STAGE_TILE_RANGES, wg::launch_forward_order(fo, tiles, stream), "forward_order");
-                fo.table = nullptr;
-            }
-        }
-        WG_STAGE(WG_STAGE_PREPROCESS, wg::launch_preprocess(fp, device_tone(tone, tone2, sh_second), geom, radii, lazy_colour, stream), "preprocess");
-        wg::SpecLimits spec;   // all zero: the classic flow
-        char* spec_chunk = nullptr;
-        bool spec_lazy = false;
-        if (tiles <= wg::BIN_MAX_TILES) {
-            if (try_split)
-                WG_STAGE(WG_STAGE_SCAN, wg::launch_split_threshold(P, geom, img, tiles, opt.near_split == 1, near_per_tile, stream), "split_threshold");
-            if (lazy_colour) WG_STAGE(WG_STAGE_PREPROCESS, wg::launch_sh_colour(fp, geom, img.split, false, stream), "sh_colour_near");
-            const bool box = opt.box_count == 1 || (opt.box_count < 0 && (P >= opt.band_list_min_p || t_last_instances_per_tile >= 1500u));
-            WG_STAGE(WG_STAGE_SCAN, wg::launch_tile_count(P, geom, img, gx, tiles, try_split, box, opt.fused_scan != 0, stream), "tile_count");
-            mbox = (debug || !opt.use_mailbox || fixed) ? nullptr : get_mailbox();
-            if (mbox) mbox->seq += 1;
-            if (fixed) {  // the caller's capacity; the lazy flow covers lists of any length
-                spec.capacity = (uint32_t)fixed_capacity;
-                spec.max_list = 0xffffffffu;
-                spec_lazy = true;
-                spec_chunk = binning_alloc(required_bytes([&](char*& c) { wg::BinningState::fromChunk(c, (size_t)spec.capacity, false); }), binning_user);
-                if (!spec_chunk) return WG_ERR_ALLOC;
-            }
-            // ---- speculative forward (option "speculative_forward", default on) ----
-            // The reference's forward pass stops in its middle for the instance count (rasterizer_impl.cu:284: it sizes the binning
-            // buffer), the GPU idles while the host then launches the rest.  Frames of one training run resemble one another, so the
-            // count of THIS frame is predicted from this thread's recent frames of the same shape: the binning buffer is allocated
-            // with a margin, everything behind the count is enqueued at once -- each kernel guarded by the verdict tile_scan leaves
-            // in BinStats::spec_fail -- and the host looks at the mailbox only after its last launch, by which time the count has
-            // usually long arrived.  A frame that does not fit (more instances than the buffer holds, a list longer than the launched
-            // sort network covers) runs none of the guarded kernels; the host then re-issues the tail with the real numbers, i.e.
-            // falls back to the classic flow for that frame.  Results are the classic flow's, bit for bit.
-            if (!fixed && mbox && opt.speculative > 0 && !opt.force_global_sort && t_spec.usable(P, width, height)) {
-                const uint64_t cap64 = (uint64_t)t_spec.max_rendered() * (100u + (uint32_t)opt.spec_margin_pct) / 100u + 4096u;
-                const uint32_t longest = t_spec.max_longest() + t_spec.max_longest() / 8u + 16u;
-                // the split's decision is taken on the device: when it is attempted the (superset) lazy flow is enqueued
-                spec_lazy = lazy_for(try_split, longest);
-                const uint32_t cover = spec_lazy ? 0xffffffffu : (longest <= 1024u ? 1024u : longest <= 2048u ? 2048u : longest <= 4096u ? 4096u : wg::TILE_SORT_MAX);
-                if (cap64 < 0x7fffffffull && (spec_lazy || longest <= wg::TILE_SORT_MAX)) {
-                    spec.capacity = (uint32_t)cap64;
-                    spec.max_list = cover;
-                    spec_chunk = binning_alloc(required_bytes([&](char*& c) { wg::BinningState::fromChunk(c, (size_t)spec.capacity, false); }), binning_user);
-                    if (!spec_chunk) return WG_ERR_ALLOC;
-                }
-            }
-            WG_STAGE(WG_STAGE_SCAN, wg::launch_tile_scan(img, tiles, mbox ? mbox->dev : nullptr, mbox ? mbox->seq : 0, try_split, spec, opt.fused_scan != 0, fo, stream), "tile_scan");
-            // "speculative_forward" = 2: do not even look at the verdict before returning -- the thread's next call does (settle_deferred)
-            const bool deferred = !fixed && spec.capacity != 0u && opt.speculative == 2;
-            if (spec.capacity != 0u) {
-                wg::BinningState sbin = wg::BinningState::fromChunk(spec_chunk, (size_t)spec.capacity, false);
-                const uint32_t r_hint = fixed ? (t_spec.usable(P, width, height) ? std::min(t_spec.last_rendered(), spec.capacity) : spec.capacity) : t_spec.last_rendered();
-                const int st_ = enqueue_tail(sbin, r_hint, spec.max_list == 0xffffffffu ? 0u : spec.max_list, spec_lazy, try_split, img.stats);
-                if (st_ != WG_OK) return st_;
-                if (fixed || deferred) {
-                    // A frame that does not fit leaves nothing rendered: make that impossible to miss (NaN image and accumulation) and
-                    // safe to differentiate (no walked instance anywhere: the backward pass returns zeros); wg_forward_status tells.
-                    WG_STAGE(WG_STAGE_RENDER_FORWARD, wg::launch_poison_unfit(img, width, height, tiles, out_color, out_color2, stream), "poison_unfit");
-                    if (deferred) {
-                        t_deferred.pending = true;
-                        t_deferred.seq = mbox->seq;
-                        t_deferred.P = P; t_deferred.W = width; t_deferred.H = height;
-                        t_deferred.stream = stream;
-                        post_ticket(img.final_T, mbox->host, mbox->seq, stream);   // (the state's first array: image_alloc's pointer, aligned)
-                    }
-                    return (int)spec.capacity;
-                }
-            }
-        } else {
-            huge_frame = true;  // tile histogram does not fit LDS: count through the per-Gaussian prefix sum instead
-            {   // tile_scan, which fills the frame's BinStats, does not run on this path: wg_forward_status must not read a fresh buffer's bytes
-                hipError_t e0 = hipMemsetAsync(img.stats, 0, sizeof(wg::BinStats), stream);
-                if (e0 != hipSuccess) return hip_fail(e0, "stats memset");
-            }
-            WG_STAGE(WG_STAGE_SCAN, wg::run_scan(geom, P, stream), "inclusive_scan");
-            WG_STAGE(WG_STAGE_SCAN, wg::launch_scan_overflow_check(geom, P, &img.stats->max_tile_count, stream), "scan_overflow_check");
-        }
-        // the one host rendezvous of the forward pass (rasterizer_impl.cu:284) -- behind the frame's last launch when speculating
-        wg::BinStats st{};
-        hipError_t e;
-        bool have_stats = false;
-        if (mbox) {
-            // poll the mailbox (bounded: ~2 s, then fall back to a real synchronise so that a failed launch is reported)
-            const auto t0 = std::chrono::steady_clock::now();
-            bool waited = false;
-            have_stats = read_mailbox(mbox, mbox->seq, st, &waited);
-            t_wait.record(waited, std::chrono::steady_clock::now() - t0);
-        }
-        if (have_stats) {
-            e = hipSuccess;
-        } else if (!huge_frame) {
-            e = hipMemcpyAsync(&st, img.stats, sizeof(st), hipMemcpyDeviceToHost, stream);
-        } else {
-            e = hipMemcpyAsync(&st.num_rendered, geom.point_offsets + (P - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(&st.max_tile_count, &img.stats->max_tile_count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-        }
-        if (e != hipSuccess) return hip_fail(e, "num_rendered readback");
-        if (!have_stats) {
-            e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) return hip_fail(e, "num_rendered readback sync");
-        }
-        if (huge_frame) {  // here max_tile_count carried the scan's overflow flag; the longest list itself is unknown on this path
-            if (st.max_tile_count != 0u) return WG_ERR_OVERFLOW;
-            st.max_tile_count = 0xffffffffu;
-        }
-        if (st.num_rendered > 0x7fffffffu) return WG_ERR_OVERFLOW;
-        num_rendered = (int)st.num_rendered;
-        max_tile_count = st.max_tile_count;
-        split_active = try_split && !huge_frame && st.split_active != 0u;
-        t_last_instances_per_tile = tiles > 0 ? st.num_rendered / (uint32_t)tiles : 0u;
-        if (!huge_frame) t_spec.push(P, width, height, st.num_rendered, st.max_tile_count);
-        if (spec.capacity != 0u) {
-            if (st.spec_fail == 0u) rendered = true;
-            t_wait.spec_frames += 1;
-            t_wait.spec_misses += st.spec_fail != 0u ? 1 : 0;
-        }
+// Everything in front of the tile scan: the per-Gaussian kernel and the per-tile counts (a frame too large for the LDS histogram: the prefix sum).
+// fo: the forward render kernel's launch order, eight workgroups riding along in the tile scan's launch -- or a launch of its own, first in the stream.
+int ForwardFrame::preprocess_and_count(wg::FwdOrderArgs& fo) const {
+    if (!order_table) {   // (what wg_view_image's order_key says then: no row)
+        hipError_t e0 = hipMemsetAsync(img.order_key, 0xff, sizeof(uint32_t), stream);
+        if (e0 != hipSuccess) return hip_fail(e0, "order_key memset");
     } else {
-        hipError_t e = hipMemsetAsync(img.ranges, 0, (size_t)tiles * sizeof(uint2), stream);
-        if (e == hipSuccess) e = hipMemsetAsync(img.stats, 0, sizeof(wg::BinStats), stream);   // (no Gaussians: nothing rendered, fits)
-        if (e != hipSuccess) return hip_fail(e, "ranges memset");
+        fo.viewmatrix = a.viewmatrix; fo.projmatrix = a.projmatrix; fo.W = width; fo.H = height; fo.table = order_table; fo.slots = order_slots;
+        fo.stride = ORDER_STRIDE; fo.order = img.order_fwd; fo.key_out = img.order_key; fo.period = (uint32_t)std::max(opt.order_period, 0);
+        if (tiles > wg::BIN_MAX_TILES || opt.fused_scan) {   // no stand-alone tile scan on these paths: a launch of its own, first in the stream
+            WG_STAGE(WG_STAGE_TILE_RANGES, wg::launch_forward_order(fo, tiles, stream), "forward_order");
+            fo.table = nullptr;
+        }
     }
-    if (rendered) return num_rendered;
-
-    const bool lazy = lazy_for(split_active, max_tile_count);
-    const bool global_sort = opt.force_global_sort || huge_frame || (!lazy && max_tile_count > wg::TILE_SORT_MAX);
-    size_t bin_bytes = required_bytes([&](char*& c) { wg::BinningState::fromChunk(c, (size_t)num_rendered, global_sort); });
-    char* bin_chunk = binning_alloc(bin_bytes, binning_user);   // (a second call of this frame after a speculation that did not hold)
-    if (!bin_chunk) return WG_ERR_ALLOC;
-    wg::BinningState bin = wg::BinningState::fromChunk(bin_chunk, (size_t)num_rendered, global_sort);
-
-    if (huge_frame && num_rendered == 0) {
-        hipError_t e = hipMemsetAsync(img.ranges, 0, (size_t)tiles * sizeof(uint2), stream);
-        if (e != hipSuccess) return hip_fail(e, "ranges memset");
+    WG_STAGE(WG_STAGE_PREPROCESS, wg::launch_preprocess(fp, device_tone(a.tone, a.tone2, a.sh_second != 0), geom, a.radii, lazy_colour, stream), "preprocess");
+    if (!huge_frame) {
+        if (try_split)
+            WG_STAGE(WG_STAGE_SCAN, wg::launch_split_threshold(P, geom, img, tiles, opt.near_split == 1, near_per_tile, stream), "split_threshold");
+        if (lazy_colour) WG_STAGE(WG_STAGE_PREPROCESS, wg::launch_sh_colour(fp, geom, img.split, false, stream), "sh_colour_near");
+        const bool box = opt.box_count == 1 || (opt.box_count < 0 && (P >= opt.band_list_min_p || t_split.last_instances_per_tile >= 1500u));
+        WG_STAGE(WG_STAGE_SCAN, wg::launch_tile_count(P, geom, img, gx, tiles, try_split, box, opt.fused_scan != 0, stream), "tile_count");
+    } else {
+        // tile_scan, which fills the frame's BinStats, does not run on this path: wg_forward_status must not read a fresh buffer's bytes
+        hipError_t e0 = hipMemsetAsync(img.stats, 0, sizeof(wg::BinStats), stream);
+        if (e0 != hipSuccess) return hip_fail(e0, "stats memset");
+        WG_STAGE(WG_STAGE_SCAN, wg::run_scan(geom, P, stream), "inclusive_scan");
+        WG_STAGE(WG_STAGE_SCAN, wg::launch_scan_overflow_check(geom, P, &img.stats->max_tile_count, stream), "scan_overflow_check");
     }
-    if (num_rendered > 0 && !global_sort) {
-        const int st_ = enqueue_tail(bin, (uint32_t)num_rendered, max_tile_count, lazy, split_active, nullptr);
-        return st_ != WG_OK ? st_ : num_rendered;
+    return WG_OK;
+}
+// The tile scan of the LDS binning path and what is enqueued behind it BEFORE the count is known: everything (a fixed capacity, a prediction)
+// or nothing (spec stays all zero: the classic flow).  WG_OK: go on to the rendezvous; anything else is what the call returns (an error, or the
+// capacity of a fixed-capacity / deferred frame, whose work ends here).
+int ForwardFrame::scan_and_speculate(const wg::FwdOrderArgs& fo, wg::SpecLimits& spec) {
+    bool spec_lazy = false;
+    mbox = (debug || !opt.use_mailbox || fixed) ? nullptr : get_mailbox();
+    if (mbox) mbox->seq += 1;
+    if (fixed) {  // the caller's capacity; the lazy flow covers lists of any length
+        spec.capacity = (uint32_t)a.binning_capacity;
+        spec.max_list = 0xffffffffu;
+        spec_lazy = true;
     }
+    // ---- speculative forward (option "speculative_forward", default on) ----
+    // The reference's forward pass stops in its middle for the instance count (rasterizer_impl.cu:284: it sizes the binning
+    // buffer), the GPU idles while the host then launches the rest.  Frames of one training run resemble one another, so the
+    // count of THIS frame is predicted from this thread's recent frames of the same shape: the binning buffer is allocated
+    // with a margin, everything behind the count is enqueued at once -- each kernel guarded by the verdict tile_scan leaves
+    // in BinStats::spec_fail -- and the host looks at the mailbox only after its last launch, by which time the count has
+    // usually long arrived.  A frame that does not fit (more instances than the buffer holds, a list longer than the launched
+    // sort network covers) runs none of the guarded kernels; the host then re-issues the tail with the real numbers, i.e.
+    // falls back to the classic flow for that frame.  Results are the classic flow's, bit for bit.
+    if (!fixed && mbox && opt.speculative > 0 && !opt.force_global_sort && t_spec.usable(P, width, height)) {
+        const uint64_t cap64 = (uint64_t)t_spec.max_rendered() * (100u + (uint32_t)opt.spec_margin_pct) / 100u + 4096u;
+        const uint32_t longest = t_spec.max_longest() + t_spec.max_longest() / 8u + 16u;
+        // the split's decision is taken on the device: when it is attempted the (superset) lazy flow is enqueued
+        spec_lazy = lazy_for(try_split, longest);
+        const uint32_t cover = spec_lazy ? 0xffffffffu : (longest <= 1024u ? 1024u : longest <= 2048u ? 2048u : longest <= 4096u ? 4096u : wg::TILE_SORT_MAX);
+        if (cap64 < 0x7fffffffull && (spec_lazy || longest <= wg::TILE_SORT_MAX)) {
+            spec.capacity = (uint32_t)cap64;
+            spec.max_list = cover;
+        }
+    }
+    char* spec_chunk = spec.capacity == 0u ? nullptr : a.binning_alloc(required_bytes([&](char*& c) { wg::BinningState::fromChunk(c, (size_t)spec.capacity, false); }), a.binning_user);
+    if (spec.capacity != 0u && !spec_chunk) return WG_ERR_ALLOC;
+    WG_STAGE(WG_STAGE_SCAN, wg::launch_tile_scan(img, tiles, mbox ? mbox->dev : nullptr, mbox ? mbox->seq : 0, try_split, spec, opt.fused_scan != 0, fo, stream), "tile_scan");
+    if (spec.capacity == 0u) return WG_OK;
+    // "speculative_forward" = 2: do not even look at the verdict before returning -- the thread's next call does (settle_deferred)
+    const bool deferred = !fixed && opt.speculative == 2;
+    wg::BinningState sbin = wg::BinningState::fromChunk(spec_chunk, (size_t)spec.capacity, false);
+    const uint32_t r_hint = fixed ? (t_spec.usable(P, width, height) ? std::min(t_spec.last_rendered(), spec.capacity) : spec.capacity) : t_spec.last_rendered();
+    const int st_ = enqueue_tail(sbin, r_hint, spec.max_list == 0xffffffffu ? 0u : spec.max_list, spec_lazy, try_split, img.stats);
+    if (st_ != WG_OK) return st_;
+    if (fixed || deferred) {
+        // A frame that does not fit leaves nothing rendered: make that impossible to miss (NaN image and accumulation) and
+        // safe to differentiate (no walked instance anywhere: the backward pass returns zeros); wg_forward_status tells.
+        WG_STAGE(WG_STAGE_RENDER_FORWARD, wg::launch_poison_unfit(img, width, height, tiles, a.out_color, out_color2, stream), "poison_unfit");
+        if (deferred) {
+            t_deferred = {true, mbox->seq, P, width, height, stream};
+            post_ticket(img.final_T, mbox->host, mbox->seq, stream);   // (the state's first array: image_alloc's pointer, aligned)
+        }
+        return (int)spec.capacity;
+    }
+    return WG_OK;
+}
+// Everything behind the count on the LDS binning path: scatter -> per-tile sort (full, or lazy front) -> render -> [fix-up ->
+// far scatter -> fix-up].  R sizes the scatter's staging passes only; `longest` picks the sort network; `far` = the split may be
+// active (its two extra launches return at once when it is not, or when no tile asked); guard = the frame's BinStats when the
+// kernels are enqueued BEFORE the count is known (speculation), nullptr otherwise.
+int ForwardFrame::enqueue_tail(const wg::BinningState& bin, uint32_t R, uint32_t longest, bool lazy, bool far, const wg::BinStats* guard) const {
+    const int code_bits = code_bits_for(lazy);
+    uint32_t emit = R;  // what the scatter will emit, for the sizing of its staging passes: everything, or about near_per_tile per tile
+    if (far) emit = (uint32_t)std::min<uint64_t>(emit, (uint64_t)near_per_tile * (uint64_t)tiles * 5u / 4u);
+    WG_STAGE(WG_STAGE_DUPLICATE_KEYS, wg::launch_tile_scatter(P, geom, img, bin, gx, tiles, emit, code_bits, opt.staged_scatter, opt.staged_cap, try_split, guard, stream), "tile_scatter");
+    if (lazy) WG_STAGE(WG_STAGE_SORT, wg::launch_tile_sort_lazy(img, bin, geom, tiles, code_bits, opt.lazy, try_split, guard, stream), "tile_sort_lazy");
+    else WG_STAGE(WG_STAGE_SORT, wg::launch_tile_sort(img, bin, geom, tiles, longest, guard, stream), "tile_sort");
+    WG_STAGE(WG_STAGE_RENDER_FORWARD,
+             wg::launch_render_forward(width, height, gx, gy, img, bin, geom, a.subpixel_offset, a.background, a.out_color, out_color2, lazy, opt.exact_compositing != 0, guard, order_table, order_slots, ORDER_STRIDE, stream),
+             "render_forward");
+    if (lazy) {
+        WG_STAGE(WG_STAGE_RENDER_FIXUP,
+                 wg::launch_render_fixup(code_bits, width, height, gx, gy, img, bin, geom, a.subpixel_offset, a.background, a.out_color, out_color2, opt.lazy, try_split, 0, opt.exact_compositing != 0, (wg::HostMailbox*)nullptr, guard, stream),
+                 "render_fixup");
+        if (far) {  // all return at once unless some tile ran out of near instances with pixels still accumulating
+            if (lazy_colour) WG_STAGE(WG_STAGE_PREPROCESS, wg::launch_sh_colour(fp, geom, img.split, true, stream), "sh_colour_far");
+            WG_STAGE(WG_STAGE_DUPLICATE_KEYS, wg::launch_tile_scatter_far(P, geom, img, bin, gx, tiles, code_bits, guard, stream), "tile_scatter_far");
+            WG_STAGE(WG_STAGE_RENDER_FIXUP,
+                     wg::launch_render_fixup(code_bits, width, height, gx, gy, img, bin, geom, a.subpixel_offset, a.background, a.out_color, out_color2, opt.lazy, true, 1, opt.exact_compositing != 0, mbox ? mbox->dev : (wg::HostMailbox*)nullptr, guard, stream),
+                     "render_fixup_far");
+        }
+    }
+    return WG_OK;
+}
+// The one host rendezvous of the forward pass (rasterizer_impl.cu:284) -- behind the frame's last launch when speculating: the mailbox, else a copy and a synchronise.
+int ForwardFrame::rendezvous(wg::BinStats& st) const {
+    bool have_stats = false;
+    if (mbox) {
+        // poll the mailbox (bounded: ~2 s, then fall back to a real synchronise so that a failed launch is reported)
+        const auto t0 = std::chrono::steady_clock::now();
+        bool waited = false;
+        have_stats = read_mailbox(mbox, mbox->seq, st, &waited);
+        t_wait.record(waited, std::chrono::steady_clock::now() - t0);
+    }
+    if (!have_stats) {
+        hipError_t e = huge_frame ? hipMemcpyAsync(&st.num_rendered, geom.point_offsets + (P - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream)
+                                  : hipMemcpyAsync(&st, img.stats, sizeof(st), hipMemcpyDeviceToHost, stream);
+        if (huge_frame && e == hipSuccess) e = hipMemcpyAsync(&st.max_tile_count, &img.stats->max_tile_count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+        if (e != hipSuccess) return hip_fail(e, "num_rendered readback");
+        e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) return hip_fail(e, "num_rendered readback sync");
+    }
+    if (huge_frame) {  // here max_tile_count carried the scan's overflow flag; the longest list itself is unknown on this path
+        if (st.max_tile_count != 0u) return WG_ERR_OVERFLOW;
+        st.max_tile_count = 0xffffffffu;
+    }
+    if (st.num_rendered > 0x7fffffffu) return WG_ERR_OVERFLOW;
+    return WG_OK;
+}
+// The reference's binning (duplicate keys, one global radix sort) and the render kernel behind it; a frame without instances only renders its background.
+int ForwardFrame::global_sort_tail(const wg::BinningState& bin, int num_rendered) const {
     if (num_rendered > 0) {
         if (!huge_frame) WG_STAGE(WG_STAGE_SCAN, wg::run_scan(geom, P, stream), "inclusive_scan");
         WG_STAGE(WG_STAGE_DUPLICATE_KEYS, wg::launch_duplicate_keys(P, geom, bin, gx, stream), "duplicate_keys");
-        const int bit = (int)wg::higher_msb((uint32_t)tiles);  // rasterizer_impl.cu:303
-        WG_STAGE(WG_STAGE_SORT, wg::run_sort(bin, num_rendered, 32 + bit, stream), "radix_sort_pairs");
+        WG_STAGE(WG_STAGE_SORT, wg::run_sort(bin, num_rendered, 32 + (int)wg::higher_msb((uint32_t)tiles), stream), "radix_sort_pairs");  // rasterizer_impl.cu:303
         // tile_scan already produced ranges identical to identifyTileRanges on the sorted keys; only frames
         // too large for the LDS histogram need the key-boundary pass
         if (huge_frame) WG_STAGE(WG_STAGE_TILE_RANGES, wg::launch_tile_ranges(num_rendered, bin, img, tiles, stream), "tile_ranges");
     }
     WG_STAGE(WG_STAGE_RENDER_FORWARD,
-             wg::launch_render_forward(width, height, gx, gy, img, bin, geom, subpixel_offset, background, out_color, out_color2, false, opt.exact_compositing != 0, nullptr, order_table, order_slots, ORDER_STRIDE, stream),
+             wg::launch_render_forward(width, height, gx, gy, img, bin, geom, a.subpixel_offset, a.background, a.out_color, out_color2, false, opt.exact_compositing != 0, nullptr, order_table, order_slots, ORDER_STRIDE, stream),
              "render_forward");
     return num_rendered;
+}
+
+// check -> allocate and carve -> decide split / lazy colour -> preprocess and count -> speculate or not -> rendezvous -> tail
+static int forward_impl(const wg_forward_args& a) {
+    const wg::Options opt = call_options_snapshot(a.options);
+    if (const int checked = check_forward_args(a, opt); checked != WG_OK) return checked;
+    ForwardFrame f{a, opt};
+    const int P = f.P, tiles = f.tiles;
+
+    const bool band_lists = (size_t)P >= (size_t)opt.band_list_min_p;  // size and carving from the same snapshot
+    char* geom_chunk = a.geometry_alloc(required_bytes([&](char*& c) { wg::GeometryState::fromChunk(c, (size_t)P, band_lists); }), a.geometry_user);
+    char* img_chunk = a.image_alloc(wg_image_buffer_size(a.width, a.height), a.image_user);
+    if (!geom_chunk || !img_chunk) return WG_ERR_ALLOC;
+    remember_mode(img_chunk, opt.exact_compositing ? 1 : 0);
+    f.geom = wg::GeometryState::fromChunk(geom_chunk, (size_t)P, band_lists);
+    f.img = wg::ImageState::fromChunk(img_chunk, (size_t)a.width * a.height, (size_t)tiles);
+    f.fp = forward_params(a, opt, f.gx, f.gy);
+    f.order_table = (P > 0 && !f.debug) ? order_table_for(opt, tiles, f.stream, &f.order_slots) : nullptr;
+
+    f.near_per_tile = t_split.next_aim(opt, P, tiles);
+    const bool backoff = opt.near_split < 0 && t_split.backoff > 0;
+    if (backoff) t_split.backoff--;
+    // Automatic mode attempts it for large scenes and whenever this host thread's previous frame was dense (a performance hint only:
+    // the threshold pass costs ~15 us, the results are the same either way).
+    f.try_split = P > 0 && tiles <= wg::BIN_MAX_TILES && opt.lazy.enabled && !opt.force_global_sort && opt.near_split != 0 &&
+                  wg::GeometryState::band_lists_possible((size_t)P) &&
+                  (opt.near_split == 1 || P >= opt.band_list_min_p || t_split.last_instances_per_tile >= wg::SPLIT_DENSE_AVG) && !backoff;
+    // Frames that attempt the split with plain SH colours colour their Gaussians LAZILY: the per-Gaussian kernel leaves the colour out (and the
+    // 192-byte SH block unread), the near Gaussians are coloured once the threshold is known, the far ones only if a tile asks for its far
+    // instances (preprocess.hip: GEOM_ONLY, sh_colour_kernel).  Same colours, bit for bit, for every Gaussian the walk can reach.
+    f.lazy_colour = f.try_split && opt.lazy_colour != 0 && P >= opt.lazy_colour_min_p && a.shs != nullptr && a.colors_precomp == nullptr && a.tone == nullptr && a.tone2 == nullptr &&
+                    !a.sh_second && f.out_color2 == nullptr && a.raw == nullptr;   // (plain SH colours of activated parameters: the combinations the suite holds)
+
+    wg::BinStats st{};
+    if (P > 0) {
+        wg::FwdOrderArgs fo;
+        int status = f.preprocess_and_count(fo);
+        if (status != WG_OK) return status;
+        wg::SpecLimits spec;   // all zero: the classic flow
+        if (!f.huge_frame && (status = f.scan_and_speculate(fo, spec)) != WG_OK) return status;
+        if ((status = f.rendezvous(st)) != WG_OK) return status;
+        t_split.last_instances_per_tile = tiles > 0 ? st.num_rendered / (uint32_t)tiles : 0u;
+        if (!f.huge_frame) t_spec.push(P, a.width, a.height, st.num_rendered, st.max_tile_count);
+        if (spec.capacity != 0u) {
+            t_wait.spec_frames += 1;
+            t_wait.spec_misses += st.spec_fail != 0u ? 1 : 0;
+            if (st.spec_fail == 0u) return (int)st.num_rendered;   // the speculation held: the render kernels of this frame are already in the stream
+        }
+    } else {
+        hipError_t e = hipMemsetAsync(f.img.ranges, 0, (size_t)tiles * sizeof(uint2), f.stream);
+        if (e == hipSuccess) e = hipMemsetAsync(f.img.stats, 0, sizeof(wg::BinStats), f.stream);   // (no Gaussians: nothing rendered, fits)
+        if (e != hipSuccess) return hip_fail(e, "ranges memset");
+    }
+    const int num_rendered = (int)st.num_rendered;
+    const uint32_t max_tile_count = st.max_tile_count;
+    const bool split_active = f.try_split && !f.huge_frame && st.split_active != 0u;
+    const bool lazy = f.lazy_for(split_active, max_tile_count);
+    const bool global_sort = opt.force_global_sort || f.huge_frame || (!lazy && max_tile_count > wg::TILE_SORT_MAX);
+    char* bin_chunk = a.binning_alloc(required_bytes([&](char*& c) { wg::BinningState::fromChunk(c, (size_t)num_rendered, global_sort); }), a.binning_user);   // (a second call of this frame after a speculation that did not hold)
+    if (!bin_chunk) return WG_ERR_ALLOC;
+    wg::BinningState bin = wg::BinningState::fromChunk(bin_chunk, (size_t)num_rendered, global_sort);
+    if (f.huge_frame && num_rendered == 0) {
+        hipError_t e = hipMemsetAsync(f.img.ranges, 0, (size_t)tiles * sizeof(uint2), f.stream);
+        if (e != hipSuccess) return hip_fail(e, "ranges memset");
+    }
+    if (num_rendered > 0 && !global_sort) {
+        const int st_ = f.enqueue_tail(bin, (uint32_t)num_rendered, max_tile_count, lazy, split_active, nullptr);
+        return st_ != WG_OK ? st_ : num_rendered;
+    }
+    return f.global_sort_tail(bin, num_rendered);
 }
 
 // wg_recolor_parent (include/wg_rasterizer.h): other precomputed colours over a parent call's projection, binning and per-pixel stops
@@ -1098,12 +1119,7 @@ static int backward_impl(const wg_backward_args& a) {
     const wg_raw_gaussians* raw = a.raw;
     const bool sh_second = a.sh_second != 0;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    wg::Options opt = options_snapshot();
-    {   // the result-affecting switches are the CALL's (wg_call_options), never the process's
-        const wg_call_options dflt = WG_CALL_OPTIONS_DEFAULT;
-        const wg_call_options& co = a.options ? *a.options : dflt;
-        opt.exact_compositing = co.exact_compositing != 0; opt.deterministic_backward = co.deterministic_backward != 0; opt.grad_record = co.grad_record != 0;
-    }
+    const wg::Options opt = call_options_snapshot(a.options);
     if (image_buffer != nullptr && P > 0) {   // the frame was composited with the other arithmetic: its stored decisions are not this call's
         const int fwd_mode = remembered_mode(image_buffer);
         if (fwd_mode >= 0 && fwd_mode != (opt.exact_compositing ? 1 : 0)) return WG_ERR_INVALID_ARGUMENT;
@@ -1122,8 +1138,7 @@ static int backward_impl(const wg_backward_args& a) {
         if (tone2 != nullptr && ((tone2->mul != nullptr && tone2->dL_dmul == nullptr) || (tone2->offset != nullptr && tone2->dL_doffset == nullptr))) return WG_ERR_INVALID_ARGUMENT;
     }
     if (image_buffer != nullptr) {   // a deferred forward call's verdict, before anything is differentiated (found by its image buffer: the
-        const void* key = reinterpret_cast<const void*>((reinterpret_cast<uintptr_t>(image_buffer) + wg::ALIGN - 1) & ~(uintptr_t)(wg::ALIGN - 1));
-        const int verdict = check_ticket(key, stream);   // backward pass usually runs on torch's autograd thread, not the forward's)
+        const int verdict = check_ticket(image_key(image_buffer), stream);   // backward pass usually runs on torch's autograd thread, not the forward's)
         if (verdict != WG_OK) return verdict;
     }
     const int g_grad_record = opt.grad_record;
@@ -1276,6 +1291,54 @@ int wg_view_image(char* image_buffer, int width, int height, wg_image_view* out)
     return WG_OK;
 }
 
+// ---- the options by name: ONE table, walked by wg_set_option and wg_get_option alike (docs/OPTIONS.md words it for people) ----
+// Flag stores value != 0; Tri -1 (negative), 0 or 1 (positive); ClampLow max(value, lo): these never refuse.  Range refuses values outside
+// [lo, hi], ZeroOneOr everything but 0, 1 and [lo, hi].  after_set: what else a successful set does to the CALLING thread's state.
+enum class OptKind { Flag, Tri, Range, ClampLow, ZeroOneOr };
+struct OptionRow {
+    const char* name;
+    int (*get)(const wg::Options&);
+    void (*set)(wg::Options&, int);
+    OptKind kind; int lo, hi;
+    void (*after_set)();
+};
+#define WG_OPTION(name, member, ...) {name, [](const wg::Options& o) { return (int)o.member; }, [](wg::Options& o, int v) { o.member = static_cast<decltype(o.member)>(v); }, __VA_ARGS__}
+static const OptionRow g_option_rows[] = {
+    WG_OPTION("force_global_sort", force_global_sort, OptKind::Flag, 0, 0, nullptr),
+    WG_OPTION("host_mailbox", use_mailbox, OptKind::Flag, 0, 0, nullptr),
+    WG_OPTION("geometry_reuse", geometry_reuse, OptKind::Flag, 0, 0, nullptr),
+    WG_OPTION("fused_scan", fused_scan, OptKind::Flag, 0, 0, nullptr),
+    WG_OPTION("forward_order", forward_order, OptKind::Flag, 0, 0, nullptr),
+    WG_OPTION("forward_order_slots", forward_order_slots, OptKind::Range, 0, 1 << 16, nullptr),   // (read when a device's table is allocated)
+    WG_OPTION("order_period", order_period, OptKind::Range, 0, 4096, nullptr),
+    WG_OPTION("backward_order_period", backward_order_period, OptKind::Range, 0, 4096, nullptr),
+    WG_OPTION("lazy_colour", lazy_colour, OptKind::Flag, 0, 0, nullptr),
+    WG_OPTION("lazy_colour_min_p", lazy_colour_min_p, OptKind::Range, 0, 0x7fffffff, nullptr),
+    WG_OPTION("sh_stream", sh_stream, OptKind::Tri, 0, 0, nullptr),
+    WG_OPTION("sh_stream_max_p", sh_stream_max_p, OptKind::Range, 0, 0x7fffffff, nullptr),
+    WG_OPTION("speculative_forward", speculative, OptKind::Range, 0, 2, [] { t_spec.clear(); t_wait.clear(); t_deferred.pending = false; }),   // (a deferred frame still pending is dropped: its verdict goes unread)
+    WG_OPTION("spec_margin_pct", spec_margin_pct, OptKind::Range, 0, 1000, nullptr),
+    WG_OPTION("band_list_min_p", band_list_min_p, OptKind::ClampLow, 1, 0, nullptr),
+    WG_OPTION("near_split", near_split, OptKind::Tri, 0, 0, [] { t_split.reset(true); }),   // (also clears the calling thread's back-off and density hint: a fresh start)
+    WG_OPTION("near_per_tile", near_per_tile, OptKind::ClampLow, 0, 0, nullptr),
+    WG_OPTION("near_adapt", near_adapt, OptKind::Flag, 0, 0, [] { t_split.reset(false); }),   // (also resets the calling thread's controller and drops a report still waiting in its mailbox)
+    WG_OPTION("box_count", box_count, OptKind::Tri, 0, 0, nullptr),
+    WG_OPTION("depth_codes", depth_codes, OptKind::ZeroOneOr, 8, 12, nullptr),
+    WG_OPTION("staged_scatter", staged_scatter, OptKind::Tri, 0, 0, nullptr),
+    WG_OPTION("staged_scatter_cap", staged_cap, OptKind::ClampLow, 0, 0, nullptr),
+    WG_OPTION("lazy_sort", lazy.enabled, OptKind::Flag, 0, 0, nullptr),
+    // min_len >= 256 (the selection samples 256 entries) and min_len, cap <= 2048 (the 8-keys-per-thread network)
+    WG_OPTION("lazy_min_len", lazy.min_len, OptKind::Range, 256, 2048, nullptr),
+    WG_OPTION("lazy_target", lazy.target, OptKind::Range, 1, 2048, nullptr),
+    WG_OPTION("lazy_cap", lazy.cap, OptKind::Range, 1, 2048, nullptr),
+};
+#undef WG_OPTION
+static const OptionRow* find_option(const char* name) {
+    for (const OptionRow& r : g_option_rows)
+        if (std::strcmp(name, r.name) == 0) return &r;
+    return nullptr;
+}
+
 int wg_set_option(const char* name, int value) {
     if (!name) return WG_ERR_INVALID_ARGUMENT;
     if (std::strcmp(name, "roctx") == 0) {  // WG_ERR_INVALID_ARGUMENT when no marker library can be loaded
@@ -1288,68 +1351,28 @@ int wg_set_option(const char* name, int value) {
         order_tables_release();
         return det_scratch_release();
     }
+    const OptionRow* r = find_option(name);   // (the read-only names are not in the table: refused like any unknown one)
+    if (!r) return WG_ERR_INVALID_ARGUMENT;
+    switch (r->kind) {
+        case OptKind::Flag: value = value != 0; break;
+        case OptKind::Tri: value = value < 0 ? -1 : (value != 0); break;
+        case OptKind::Range: if (value < r->lo || value > r->hi) return WG_ERR_INVALID_ARGUMENT; break;
+        case OptKind::ClampLow: value = std::max(value, r->lo); break;
+        case OptKind::ZeroOneOr: if (value != 0 && value != 1 && (value < r->lo || value > r->hi)) return WG_ERR_INVALID_ARGUMENT; break;
+    }
     std::lock_guard<std::mutex> l(g_opt_mu);
-    wg::Options& o = g_opt;
-    if (std::strcmp(name, "force_global_sort") == 0) { o.force_global_sort = value != 0; return WG_OK; }
-    if (std::strcmp(name, "host_mailbox") == 0) { o.use_mailbox = value != 0; return WG_OK; }
-    if (std::strcmp(name, "geometry_reuse") == 0) { o.geometry_reuse = value != 0; return WG_OK; }
-    if (std::strcmp(name, "fused_scan") == 0) { o.fused_scan = value != 0; return WG_OK; }
-    if (std::strcmp(name, "forward_order") == 0) { o.forward_order = value != 0; return WG_OK; }
-    if (std::strcmp(name, "forward_order_slots") == 0) { if (value < 0 || value > (1 << 16)) return WG_ERR_INVALID_ARGUMENT; o.forward_order_slots = value; return WG_OK; }   // (read when a device's table is allocated)
-    if (std::strcmp(name, "order_period") == 0) { if (value < 0 || value > 4096) return WG_ERR_INVALID_ARGUMENT; o.order_period = value; return WG_OK; }
-    if (std::strcmp(name, "backward_order_period") == 0) { if (value < 0 || value > 4096) return WG_ERR_INVALID_ARGUMENT; o.backward_order_period = value; return WG_OK; }
-    if (std::strcmp(name, "lazy_colour") == 0) { o.lazy_colour = value != 0; return WG_OK; }
-    if (std::strcmp(name, "lazy_colour_min_p") == 0) { if (value < 0) return WG_ERR_INVALID_ARGUMENT; o.lazy_colour_min_p = value; return WG_OK; }
-    if (std::strcmp(name, "sh_stream") == 0) { o.sh_stream = value < 0 ? -1 : (value != 0); return WG_OK; }
-    if (std::strcmp(name, "sh_stream_max_p") == 0) { if (value < 0) return WG_ERR_INVALID_ARGUMENT; o.sh_stream_max_p = value; return WG_OK; }
-    if (std::strcmp(name, "speculative_forward") == 0) {  // (a deferred frame still pending is dropped: its verdict goes unread)
-        if (value < 0 || value > 2) return WG_ERR_INVALID_ARGUMENT;
-        o.speculative = value; t_spec.clear(); t_wait.clear(); t_deferred.pending = false;
-        return WG_OK;
-    }
-    if (std::strcmp(name, "spec_margin_pct") == 0) { if (value < 0 || value > 1000) return WG_ERR_INVALID_ARGUMENT; o.spec_margin_pct = value; return WG_OK; }
-    if (std::strcmp(name, "band_list_min_p") == 0) { o.band_list_min_p = value > 0 ? value : 1; return WG_OK; }
-    if (std::strcmp(name, "near_split") == 0) {  // (also clears the calling thread's back-off and density hint: a fresh start)
-        o.near_split = value < 0 ? -1 : (value != 0);
-        t_split_backoff = 0;
-        t_near = NearAdapt();
-        t_last_instances_per_tile = 0;
-        if (t_mailbox.host) t_mailbox.host->far_report = 0ull;
-        return WG_OK;
-    }
-    if (std::strcmp(name, "near_per_tile") == 0) { o.near_per_tile = value > 0 ? value : 0; return WG_OK; }
-    if (std::strcmp(name, "near_adapt") == 0) {   // (also resets the calling thread's controller and drops a report still waiting in its mailbox)
-        o.near_adapt = value != 0; t_near = NearAdapt(); t_split_backoff = 0;
-        if (t_mailbox.host) t_mailbox.host->far_report = 0ull;
-        return WG_OK;
-    }
-    if (std::strcmp(name, "box_count") == 0) { o.box_count = value < 0 ? -1 : (value != 0); return WG_OK; }
-    if (std::strcmp(name, "depth_codes") == 0) {
-        if (value != 0 && value != 1 && (value < 8 || value > 12)) return WG_ERR_INVALID_ARGUMENT;
-        o.depth_codes = value;
-        return WG_OK;
-    }
-    if (std::strcmp(name, "staged_scatter_cap") == 0) { o.staged_cap = value > 0 ? value : 0; return WG_OK; }
-    if (std::strcmp(name, "staged_scatter") == 0) { o.staged_scatter = value < 0 ? -1 : (value != 0); return WG_OK; }
-    if (std::strcmp(name, "lazy_sort") == 0) { o.lazy.enabled = value != 0; return WG_OK; }
-    if (std::strcmp(name, "lazy_min_len") == 0 || std::strcmp(name, "lazy_target") == 0 || std::strcmp(name, "lazy_cap") == 0) {
-        // min_len >= 256 (the selection samples 256 entries) and min_len, cap <= 2048 (the 8-keys-per-thread network)
-        if (value < 1 || value > 2048) return WG_ERR_INVALID_ARGUMENT;
-        if (name[5] == 'm') { if (value < 256) return WG_ERR_INVALID_ARGUMENT; o.lazy.min_len = (uint32_t)value; }
-        else if (name[5] == 't') o.lazy.target = (uint32_t)value;
-        else o.lazy.cap = (uint32_t)value;
-        return WG_OK;
-    }
-    return WG_ERR_INVALID_ARGUMENT;
+    r->set(g_opt, value);
+    if (r->after_set) r->after_set();
+    return WG_OK;
 }
 
 int wg_get_option(const char* name) {
     if (!name) return -1;
     if (std::strcmp(name, "roctx") == 0) return g_roctx.enabled ? 1 : 0;
-    if (std::strcmp(name, "near_split_backoff") == 0) return (int)t_split_backoff;  // read-only, of the calling thread
-    if (std::strcmp(name, "near_per_tile_now") == 0) return (int)t_near.cur;        // read-only: the calling thread's adapted aim (0 = none yet)
-    if (std::strcmp(name, "near_floor_now") == 0) return (int)t_near.floor;         // read-only: the floor the adaptation does not go below (scripts/r6/near_trace.py)
-    if (std::strcmp(name, "near_far_tiles_last") == 0) return (int)t_near.last_far;  // read-only: tiles that asked for far instances in the last reported split frame
+    if (std::strcmp(name, "near_split_backoff") == 0) return (int)t_split.backoff;  // read-only, of the calling thread
+    if (std::strcmp(name, "near_per_tile_now") == 0) return (int)t_split.near.cur;        // read-only: the calling thread's adapted aim (0 = none yet)
+    if (std::strcmp(name, "near_floor_now") == 0) return (int)t_split.near.floor;         // read-only: the floor the adaptation does not go below (scripts/r6/near_trace.py)
+    if (std::strcmp(name, "near_far_tiles_last") == 0) return (int)t_split.near.last_far;  // read-only: tiles that asked for far instances in the last reported split frame
     // read-only counters of the calling thread since the last wg_set_option("speculative_forward", ...)
     if (std::strcmp(name, "spec_frames") == 0) return (int)std::min<uint64_t>(t_wait.spec_frames, 0x7fffffffu);
     if (std::strcmp(name, "spec_misses") == 0) return (int)std::min<uint64_t>(t_wait.spec_misses, 0x7fffffffu);
@@ -1357,33 +1380,8 @@ int wg_get_option(const char* name) {
     if (std::strcmp(name, "forward_polls_waited") == 0) return (int)std::min<uint64_t>(t_wait.waited, 0x7fffffffu);
     if (std::strcmp(name, "forward_wait_us_total") == 0) return (int)std::min(t_wait.wait_us, 2147483647.0);
     if (std::strcmp(name, "forward_wait_us_last") == 0) return (int)std::min(t_wait.last_wait_us, 2147483647.0);
-    const wg::Options o = options_snapshot();
-    if (std::strcmp(name, "geometry_reuse") == 0) return o.geometry_reuse;
-    if (std::strcmp(name, "fused_scan") == 0) return o.fused_scan;
-    if (std::strcmp(name, "forward_order") == 0) return o.forward_order;
-    if (std::strcmp(name, "forward_order_slots") == 0) return o.forward_order_slots;
-    if (std::strcmp(name, "order_period") == 0) return o.order_period;
-    if (std::strcmp(name, "backward_order_period") == 0) return o.backward_order_period;
-    if (std::strcmp(name, "lazy_colour") == 0) return o.lazy_colour;
-    if (std::strcmp(name, "lazy_colour_min_p") == 0) return o.lazy_colour_min_p;
-    if (std::strcmp(name, "sh_stream") == 0) return o.sh_stream;
-    if (std::strcmp(name, "sh_stream_max_p") == 0) return o.sh_stream_max_p;
-    if (std::strcmp(name, "speculative_forward") == 0) return o.speculative;
-    if (std::strcmp(name, "spec_margin_pct") == 0) return o.spec_margin_pct;
-    if (std::strcmp(name, "force_global_sort") == 0) return o.force_global_sort ? 1 : 0;
-    if (std::strcmp(name, "host_mailbox") == 0) return o.use_mailbox ? 1 : 0;
-    if (std::strcmp(name, "lazy_sort") == 0) return o.lazy.enabled ? 1 : 0;
-    if (std::strcmp(name, "depth_codes") == 0) return o.depth_codes;
-    if (std::strcmp(name, "band_list_min_p") == 0) return o.band_list_min_p;
-    if (std::strcmp(name, "staged_scatter") == 0) return o.staged_scatter;
-    if (std::strcmp(name, "near_split") == 0) return o.near_split;
-    if (std::strcmp(name, "near_per_tile") == 0) return o.near_per_tile;
-    if (std::strcmp(name, "near_adapt") == 0) return o.near_adapt;
-    if (std::strcmp(name, "box_count") == 0) return o.box_count;
-    if (std::strcmp(name, "lazy_min_len") == 0) return (int)o.lazy.min_len;
-    if (std::strcmp(name, "lazy_target") == 0) return (int)o.lazy.target;
-    if (std::strcmp(name, "lazy_cap") == 0) return (int)o.lazy.cap;
-    return -1;
+    const OptionRow* r = find_option(name);
+    return r ? r->get(options_snapshot()) : -1;
 }
 
 int wg_profile_enable(int enable) {
