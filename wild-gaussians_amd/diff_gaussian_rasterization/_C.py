@@ -9,12 +9,16 @@ three functions with the same argument order and return tuples:
                                           dL_dscales, dL_drotations)
     mark_visible(means3D, viewmatrix, projmatrix) -> bool[P]
 
-It is a thin ctypes layer over ``libwg_rasterizer.so`` (include/wg_rasterizer.h): torch is used only to
-allocate device memory and to supply the current HIP stream.  There is NO fallback: if the HIP library has
-not been built, importing this module raises.
+It is the one Python door to ``libwg_rasterizer.so`` (include/wg_rasterizer.h).  Each call is dispatched to the compiled torch binding
+(csrc/torch_binding.cpp, the default when built) or to the ctypes binding below (``_forward_ctypes`` / ``_backward_ctypes``: a variant library,
+the counting tools, a tree without the compiled module).  Both take the same arguments, refuse the same malformed calls with the same messages
+(``_check_forward_arguments`` / ``_check_backward_arguments`` here, the same checks in C++ there) and return the same tuples.  Per-call option
+resolution, the opt-in geometry reuse, the library's options, stage timing and the views into the scratch buffers live here for both.  There
+is NO fallback: if the HIP library has not been built, importing this module raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -59,7 +63,8 @@ def binding_name() -> str:
     return "ctypes" if _torch_ext is None else "torch"
 
 
-from ._abi import _ALLOC_FN, _vp, _i, _f  # noqa: E402
+from ._abi import (_ALLOC_FN, _vp, _i, _f, _ShTone, _SecondImage, _RawGaussians, _RecolorParent, _CallOptions, _ForwardArgs,  # noqa: E402
+                    _BackwardArgs)   # (pure ctypes)
 
 _lib.wg_rasterize_forward.restype = _i
 _lib.wg_rasterize_forward.argtypes = [_ALLOC_FN, _vp, _ALLOC_FN, _vp, _ALLOC_FN, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp,
@@ -67,10 +72,6 @@ _lib.wg_rasterize_forward.argtypes = [_ALLOC_FN, _vp, _ALLOC_FN, _vp, _ALLOC_FN,
 _lib.wg_rasterize_backward.restype = _i
 _lib.wg_rasterize_backward.argtypes = [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _f, _f,
                                        _vp, _vp, _vp, _vp, _vp, _vp] + [_vp] * 9 + [_i, _vp]
-
-
-from ._abi import (_ShTone, _SecondImage, _RawGaussians, _RecolorParent, _CallOptions, _ForwardArgs, _BackwardArgs)  # noqa: E402  (pure ctypes)
-
 _lib.wg_rasterize_forward_ex.restype = _i
 _lib.wg_rasterize_forward_ex.argtypes = [C.POINTER(_ForwardArgs)]
 _lib.wg_rasterize_backward_ex.restype = _i
@@ -86,14 +87,13 @@ _lib.wg_image_buffer_size.restype = C.c_size_t
 _lib.wg_image_buffer_size.argtypes = [_i, _i]
 _lib.wg_image_accumulation_offset.restype = C.c_size_t
 _lib.wg_image_accumulation_offset.argtypes = [_i, _i]
-for _name in ("wg_status_string",):
+for _name, _args in (("wg_status_string", [_i]), ("wg_last_hip_error", []), ("wg_version", [])):
     getattr(_lib, _name).restype = C.c_char_p
-    getattr(_lib, _name).argtypes = [_i]
+    getattr(_lib, _name).argtypes = _args
 _lib.wg_get_option.restype = _i
 _lib.wg_get_option.argtypes = [C.c_char_p]
-for _name in ("wg_last_hip_error", "wg_version"):
-    getattr(_lib, _name).restype = C.c_char_p
-    getattr(_lib, _name).argtypes = []
+_lib.wg_set_option.restype = _i
+_lib.wg_set_option.argtypes = [C.c_char_p, _i]
 
 
 class _GeometryView(C.Structure):
@@ -127,7 +127,6 @@ def accumulation_offset(height: int, width: int) -> int:
     return _acc_offsets[k]
 
 
-
 def _check(status: int, what: str) -> int:
     if status < 0:
         msg = _lib.wg_status_string(status).decode()
@@ -144,6 +143,10 @@ def _f32(t: torch.Tensor, device) -> torch.Tensor:
     if t.device != device or t.dtype != torch.float32:
         t = t.to(device=device, dtype=torch.float32)
     return t if t.is_contiguous() else t.contiguous()
+
+
+def _f32s(device, *tensors):
+    return [None if t is None else _f32(t, device) for t in tensors]
 
 
 def _ptr(t: torch.Tensor):
@@ -178,20 +181,97 @@ def _tone_block(sh_tone, device, P, grads=None):
     """sh_tone = (mul [P,3] or None, offset [P,3] or None, pre_clamp_max or None, post_clamp_max or None) -> (_ShTone, keep-alive).
     Beyond the reference: see wg_sh_tone in include/wg_rasterizer.h."""
     mul, offset, pre, post = sh_tone
-    keep = []
-    t = _ShTone()
-    for name, v in (("mul", mul), ("offset", offset)):
-        if v is not None:
-            v = _f32(v, device)
-            if v.numel() != 3 * P:
-                raise RuntimeError(f"sh_{name} must have 3 * P elements")
-            keep.append(v)
-            setattr(t, name, v.data_ptr())
-    t.pre_clamp_max = float("inf") if pre is None else float(pre)
-    t.post_clamp_max = float("inf") if post is None else float(post)
-    if grads is not None:
-        t.dL_dmul, t.dL_doffset = (None if g is None else g.data_ptr() for g in grads)
+    keep = _f32s(device, mul, offset)
+    t = _ShTone(*(None if v is None else v.data_ptr() for v in keep), float("inf") if pre is None else float(pre),
+                float("inf") if post is None else float(post), *(None if g is None else g.data_ptr() for g in grads or ()))
     return t, keep
+
+
+def _second_block(device, colors2=None, out_color2=None, dL_dpix2=None, dL_dcolor2=None):
+    """wg_second_image from whichever of its four tensors the call has -> (_SecondImage, keep-alive)."""
+    keep = _f32s(device, colors2, out_color2, dL_dpix2, dL_dcolor2)
+    return _SecondImage(*(None if t is None else t.data_ptr() for t in keep)), keep
+
+
+def _raw_block(device, filter_3D, raw_opacities=None):
+    """wg_raw_gaussians (raw_opacities: the backward call's) -> (_RawGaussians, keep-alive)."""
+    keep = _f32s(device, filter_3D, raw_opacities)
+    return _RawGaussians(*(None if t is None else t.data_ptr() for t in keep)), keep
+
+
+def _attach_blocks(a, opts, tone=None, tone2=None, second=None, raw=None):
+    """Hang the optional blocks, each a (struct, keep-alive) pair or None, and the per-call options on an args struct -> keep-alive list."""
+    keep = []
+    for name, block in (("tone", tone), ("tone2", tone2), ("second", second), ("raw", raw), ("options", (_CallOptions(*opts), None))):
+        if block is not None:
+            keep += block
+            setattr(a, name, C.pointer(block[0]))
+    a.sh_second = int(tone2 is not None)
+    return keep
+
+
+# ----------------------------------------------------------------------------------------------------------
+# The argument checks of both calls: a wrong-size tensor must raise, not send a kernel out of bounds (ADVICE r5).  Pure functions of shapes,
+# numel() values and which optional arguments are given.  The ctypes binding calls them; the compiled one, a module of its own whose fast
+# path pays for no Python-side check, makes the same checks in the same order with the same messages (csrc/torch_binding.cpp).
+def _rows(t, per, P):
+    return t.numel() in (0, per * P)
+
+
+def _sh_rows(sh, P):
+    return sh.numel() == 0 or (sh.dim() == 3 and sh.size(0) == P and sh.size(2) == 3)
+
+
+def _check_tone(tone, P):
+    if tone is not None and len(tone) != 4:
+        raise RuntimeError("a tone is (mul, offset, pre_clamp_max, post_clamp_max)")
+    for name, v in zip(("mul", "offset"), tone or ()):
+        if v is not None and v.numel() != 3 * P:
+            raise RuntimeError(f"sh_{name} must have 3 * P elements")
+
+
+def _check_forward_arguments(means3D, colors, opacity, scales, rotations, cov3D_precomp, sh, debug, sh_tone, binning_capacity, colors2, filter_3D, sh_second):
+    """What rasterize_gaussians refuses, after its two leading checks (means3D is (P, 3), on a HIP device)."""
+    P = means3D.size(0)
+    fixed = binning_capacity is not None
+    if filter_3D is not None and (colors2 is not None or fixed or scales.numel() == 0 or filter_3D.numel() != P):
+        raise RuntimeError("filter_3D (raw-parameter mode) needs scales and rotations, P filter values, and neither colors2 nor binning_capacity")
+    if sh_second is not None and (colors2 is not None or fixed or sh.numel() == 0 or colors.numel() != 0):
+        raise RuntimeError("sh_second (two tones of one SH block) needs SH colours and neither colors2 nor binning_capacity")
+    if colors2 is not None and (sh_tone is not None or fixed or sh.numel() != 0 or colors.numel() != 3 * P or colors2.numel() != 3 * P):
+        raise RuntimeError("colors2 needs precomputed colours of P x 3 in both sets (no SH, no sh_tone, no binning_capacity)")
+    if fixed and debug:
+        raise RuntimeError("binning_capacity (the fixed-capacity forward) has no debug mode")
+    for t, per, name in ((colors, 3, "colors_precomp"), (opacity, 1, "opacities"), (scales, 3, "scales"), (rotations, 4, "rotations"),
+                         (cov3D_precomp, 6, "cov3D_precomp")):
+        if not _rows(t, per, P):
+            raise RuntimeError(f"{name} must have {per} * P elements")
+    if not _sh_rows(sh, P):
+        raise RuntimeError("sh must have dimensions (P, M, 3)")
+    if opacity.numel() != P:
+        raise RuntimeError("opacities must have P elements")
+    _check_tone(sh_tone, P)
+    _check_tone(sh_second, P)
+    if fixed and int(binning_capacity) <= 0:
+        raise RuntimeError("binning_capacity must be positive")
+
+
+def _check_backward_arguments(means3D, radii, colors, scales, rotations, cov3D_precomp, sh, dL_dout_color, sh_tone, dL_dout_color2, raw, sh_second):
+    """What rasterize_gaussians_backward refuses, after the three mode checks it makes in front of both bindings."""
+    P = means3D.size(0)
+    if dL_dout_color.dim() != 3 or dL_dout_color.size(0) != 3:
+        raise RuntimeError("dL_dout_color must have dimensions (3, H, W)")
+    if dL_dout_color2 is not None and dL_dout_color2.numel() != dL_dout_color.numel():
+        raise RuntimeError("dL_dout_color2 must have the first image's dimensions")
+    if P != 0 and not (radii.numel() == P and _rows(colors, 3, P) and _rows(scales, 3, P) and _rows(rotations, 4, P) and _rows(cov3D_precomp, 6, P)
+                       and _sh_rows(sh, P)):
+        raise RuntimeError("a per-Gaussian argument of the backward call does not have P rows")
+    _check_tone(sh_tone, P)
+    _check_tone(sh_second, P)
+    if raw is not None and len(raw) != 2:
+        raise RuntimeError("raw is (filter_3D, raw_opacities)")
+    if raw is not None and (raw[0].numel() != P or raw[1].numel() != P):
+        raise RuntimeError("raw = (filter_3D, raw_opacities) must have P elements each")
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -317,9 +397,6 @@ def resolve_call_options(options=None):
     return (int(bool(d["exact_compositing"])), int(bool(d["deterministic_backward"])), int(bool(d["grad_record"])))
 
 
-import contextlib  # noqa: E402
-
-
 @contextlib.contextmanager
 def call_options(**kw):
     """`with _C.call_options(deterministic_backward=1): ...` -- the calling thread's defaults for the block (for callers that cannot pass
@@ -337,26 +414,25 @@ def call_options(**kw):
         d.update(saved)
 
 
-def _options_block(opts):
-    return _CallOptions(*opts)
+def _fill(a, device, P, degree, M, H, W, debug, scale_modifier, tan_fovx, tan_fovy, kernel_size, **tensors):
+    """The fields wg_forward_args and wg_backward_args share; every other pointer field by name (None or zero-sized = NULL)."""
+    a.struct_size = C.sizeof(a)
+    a.P, a.D, a.M, a.width, a.height, a.debug = P, int(degree), M, W, H, int(bool(debug))
+    a.scale_modifier, a.tan_fovx, a.tan_fovy, a.kernel_size = float(scale_modifier), float(tan_fovx), float(tan_fovy), float(kernel_size)
+    for name, t in tensors.items():
+        setattr(a, name, None if t is None else _ptr(t))
+    a.stream = _stream(device)
 
 
 def _forward_args(geom, binning, img, P, degree, M, H, W, background, means3D, sh, colors, opacity, scales, scale_modifier, rotations, cov3D_precomp,
                   viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, kernel_size, subpixel_offset, prefiltered, debug, out_color, radii, device):
     a = _ForwardArgs()
-    a.struct_size = C.sizeof(_ForwardArgs)
-    a.geometry_alloc = geom.callback
+    _fill(a, device, P, degree, M, H, W, debug, scale_modifier, tan_fovx, tan_fovy, kernel_size, background=background, means3D=means3D, shs=sh,
+          colors_precomp=colors, opacities=opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, viewmatrix=viewmatrix,
+          projmatrix=projmatrix, cam_pos=campos, subpixel_offset=subpixel_offset, out_color=out_color, radii=radii)
+    a.geometry_alloc, a.prefiltered = geom.callback, int(bool(prefiltered))
     if binning is not None:
         a.binning_alloc, a.image_alloc = binning.callback, img.callback
-    a.P, a.D, a.M, a.width, a.height, a.prefiltered, a.debug = P, int(degree), M, W, H, int(bool(prefiltered)), int(bool(debug))
-    a.scale_modifier, a.tan_fovx, a.tan_fovy, a.kernel_size = float(scale_modifier), float(tan_fovx), float(tan_fovy), float(kernel_size)
-    for name, t in (("background", background), ("means3D", means3D), ("shs", sh), ("colors_precomp", colors), ("opacities", opacity), ("scales", scales),
-                    ("rotations", rotations), ("cov3D_precomp", cov3D_precomp), ("viewmatrix", viewmatrix), ("projmatrix", projmatrix), ("cam_pos", campos),
-                    ("subpixel_offset", subpixel_offset)):
-        setattr(a, name, None if t is None else _ptr(t))
-    a.out_color = out_color.data_ptr()
-    a.radii = None if radii is None else radii.data_ptr()
-    a.stream = _stream(device)
     return a
 
 
@@ -374,63 +450,47 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
       forward_status(imgBuffer, H, W) tells the real count and whether the frame fit.
     options: per-call options (see resolve_call_options)."""
     opts = resolve_call_options(options)
-    if _torch_ext is not None and not _geometry_reuse_on:
-        # the usual path: the compiled binding (csrc/torch_binding.cpp) checks its arguments itself (same messages), nothing is remembered
-        _reuse.last = None
-        res = _torch_ext.rasterize_gaussians_ex(background, means3D, colors, opacity, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix,
-                                                projmatrix, float(tan_fovx), float(tan_fovy), float(kernel_size), subpixel_offset, int(image_height),
-                                                int(image_width), sh, int(degree), campos, bool(prefiltered), bool(debug), sh_tone, binning_capacity, colors2,
-                                                filter_3D, sh_second, opts)
-        if binning_capacity is not None:
-            _reuse.last_fixed = (res[5], int(image_height), int(image_width))
-        return res
-    if means3D.dim() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:59-61
-    if not means3D.is_cuda:
-        raise RuntimeError("means3D must live on a HIP device: this rasterizer has no CPU path")
-    device = means3D.device
-    P, H, W = means3D.size(0), int(image_height), int(image_width)
-
-    if filter_3D is not None and (colors2 is not None or binning_capacity is not None or scales.numel() == 0 or filter_3D.numel() != P):
-        raise RuntimeError("filter_3D (raw-parameter mode) needs scales and rotations, P filter values, and neither colors2 nor binning_capacity")
-    if sh_second is not None and (colors2 is not None or binning_capacity is not None or sh.numel() == 0 or colors.numel() != 0):
-        raise RuntimeError("sh_second (two tones of one SH block) needs SH colours and neither colors2 nor binning_capacity")
-    if colors2 is not None:
-        if sh_tone is not None or binning_capacity is not None or sh.numel() != 0 or colors.numel() != 3 * P or colors2.numel() != 3 * P:
-            raise RuntimeError("colors2 needs precomputed colours of P x 3 in both sets (no SH, no sh_tone, no binning_capacity)")
-    if binning_capacity is not None and debug:
-        raise RuntimeError("binning_capacity (the fixed-capacity forward) has no debug mode")
-    # precomputed colours over remembered geometry: no projection, no binning
-    reusable = (P != 0 and sh_tone is None and not debug and colors.numel() == 3 * P and sh.numel() == 0 and colors2 is None
-                and filter_3D is None and sh_second is None and _geometry_reuse_on)
+    H, W = int(image_height), int(image_width)
     key = None
-    if reusable:
-        key = _reuse_key(background, means3D, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
-                         tan_fovy, kernel_size, subpixel_offset, H, W, prefiltered, device) + (opts,)
-        last = _reuse_lookup(key)
-        if last is not None:
-            geom = _Scratch(device)
-            out_color = torch.empty((3, H, W), dtype=torch.float32, device=device)
-            colors_f, bg_f = _f32(colors, device), _f32(background, device)
-            so = None if subpixel_offset is None else _f32(subpixel_offset, device)
-            a = _forward_args(geom, None, None, P, 0, 0, H, W, bg_f, None, None, colors_f, None, None, 1.0, None, None, None, None, None, 1.0, 1.0, 0.0, so,
-                              False, False, out_color, None, device)
-            parent = _RecolorParent(last["geom"].data_ptr(), last["binning"].data_ptr(), last["img"].data_ptr(), int(last["R"]))
-            ob = _options_block(opts)
-            a.recolor, a.options = C.pointer(parent), C.pointer(ob)
-            try:
-                with torch.cuda.device(device):
-                    rendered = _lib.wg_rasterize_forward_ex(C.byref(a))
-            finally:
-                child = geom.take()
-            _check(rendered, "wg_rasterize_forward_ex (recolor)")
-            _reuse.hits += 1
-            # (a fresh radii tensor, as every call of the reference returns: 4 bytes per Gaussian)
-            return (rendered, out_color, last["radii"].clone(), child, last["binning"], last["img"])
+    if _torch_ext is not None and not _geometry_reuse_on:
+        _reuse.last = None   # the usual path: the compiled binding checks its arguments itself (same messages), nothing is remembered
     else:
-        _reuse.last = None   # any other kind of call ends the remembered one's reach
+        if means3D.dim() != 2 or means3D.size(1) != 3:
+            raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:59-61
+        if not means3D.is_cuda:
+            raise RuntimeError("means3D must live on a HIP device: this rasterizer has no CPU path")
+        _check_forward_arguments(means3D, colors, opacity, scales, rotations, cov3D_precomp, sh, debug, sh_tone, binning_capacity, colors2, filter_3D,
+                                 sh_second)
+        device, P = means3D.device, means3D.size(0)
+        # precomputed colours over remembered geometry: no projection, no binning
+        reusable = (P != 0 and sh_tone is None and not debug and colors.numel() == 3 * P and sh.numel() == 0 and colors2 is None
+                    and filter_3D is None and sh_second is None and _geometry_reuse_on)
+        if reusable:
+            key = _reuse_key(background, means3D, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
+                             tan_fovy, kernel_size, subpixel_offset, H, W, prefiltered, device) + (opts,)
+            last = _reuse_lookup(key)
+            if last is not None:
+                geom = _Scratch(device)
+                out_color = torch.empty((3, H, W), dtype=torch.float32, device=device)
+                colors_f, bg_f, so = _f32s(device, colors, background, subpixel_offset)
+                a = _forward_args(geom, None, None, P, 0, 0, H, W, bg_f, None, None, colors_f, None, None, 1.0, None, None, None, None, None, 1.0, 1.0, 0.0,
+                                  so, False, False, out_color, None, device)
+                parent = _RecolorParent(last["geom"].data_ptr(), last["binning"].data_ptr(), last["img"].data_ptr(), int(last["R"]))
+                ob = _CallOptions(*opts)
+                a.recolor, a.options = C.pointer(parent), C.pointer(ob)
+                try:
+                    with torch.cuda.device(device):
+                        rendered = _lib.wg_rasterize_forward_ex(C.byref(a))
+                finally:
+                    child = geom.take()
+                _check(rendered, "wg_rasterize_forward_ex (recolor)")
+                _reuse.hits += 1
+                # (a fresh radii tensor, as every call of the reference returns: 4 bytes per Gaussian)
+                return (rendered, out_color, last["radii"].clone(), child, last["binning"], last["img"])
+        else:
+            _reuse.last = None   # any other kind of call ends the remembered one's reach
 
-    if _torch_ext is not None:   # the compiled binding (csrc/torch_binding.cpp), when it is loaded: the whole surface but the recolouring above
+    if _torch_ext is not None:   # the compiled binding (csrc/torch_binding.cpp): the whole surface but the recolouring above
         res = _torch_ext.rasterize_gaussians_ex(background, means3D, colors, opacity, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix,
                                                 projmatrix, float(tan_fovx), float(tan_fovy), float(kernel_size), subpixel_offset, H, W, sh, int(degree),
                                                 campos, bool(prefiltered), bool(debug), sh_tone, binning_capacity, colors2, filter_3D, sh_second, opts)
@@ -438,12 +498,11 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
         res = _forward_ctypes(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
                               tan_fovy, kernel_size, subpixel_offset, H, W, sh, degree, campos, prefiltered, debug, sh_tone, binning_capacity, colors2,
                               filter_3D, sh_second, opts, device, P)
-    rendered, radii, buffers = res[0], res[2], res[3:6]
     if binning_capacity is not None:
-        _reuse.last_fixed = (buffers[2], H, W)
+        _reuse.last_fixed = (res[5], H, W)
     # (never a parent whose verdict is not in yet: see "Geometry reuse" above)
-    if key is not None and P != 0 and binning_capacity is None and _lib.wg_get_option(b"speculative_forward") != 2:
-        _reuse.last = dict(tensors=key[0], scalars=key[1], opts=key[2], R=rendered, radii=radii, geom=buffers[0], binning=buffers[1], img=buffers[2],
+    if key is not None and binning_capacity is None and _lib.wg_get_option(b"speculative_forward") != 2:
+        _reuse.last = dict(tensors=key[0], scalars=key[1], opts=key[2], R=res[0], radii=res[2], geom=res[3], binning=res[4], img=res[5],
                            epoch=_reuse_epoch)
     return res
 
@@ -451,6 +510,7 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 def _forward_ctypes(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                     kernel_size, subpixel_offset, H, W, sh, degree, campos, prefiltered, debug, sh_tone, binning_capacity, colors2, filter_3D, sh_second,
                     opts, device, P):
+    """The checked forward call through ctypes -> the reference's six, + the second image with colors2 / sh_second."""
     geom, binning, img = _Scratch(device), _Scratch(device), _Scratch(device)
     two = colors2 is not None or sh_second is not None
     if P == 0:  # rasterize_points.cu:83: nothing is launched, the image stays zero
@@ -459,42 +519,18 @@ def _forward_ctypes(background, means3D, colors, opacity, scales, rotations, sca
     # both outputs are fully written by the kernels (every pixel, every Gaussian): no need for the reference's zero fill
     out_color = torch.empty((3, H, W), dtype=torch.float32, device=device)
     radii = torch.empty((P,), dtype=torch.int32, device=device)
-    means3D = _f32(means3D, device)
-    background, colors, opacity = _f32(background, device), _f32(colors, device), _f32(opacity, device)
-    scales, rotations, cov3D_precomp = _f32(scales, device), _f32(rotations, device), _f32(cov3D_precomp, device)
-    viewmatrix, projmatrix, campos = _f32(viewmatrix, device), _f32(projmatrix, device), _f32(campos, device)
-    subpixel_offset = None if subpixel_offset is None else _f32(subpixel_offset, device)   # None: no offsets, nothing allocated or read
-    sh = _f32(sh, device)
+    out_color2 = torch.empty((3, H, W), dtype=torch.float32, device=device) if two else None
+    means3D, background, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, subpixel_offset, sh = _f32s(
+        device, means3D, background, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, subpixel_offset, sh)
     M = sh.size(1) if sh.numel() != 0 else 0  # rasterize_points.cu:85-89
     a = _forward_args(geom, binning, img, P, degree, M, H, W, background, means3D, sh, colors, opacity, scales, scale_modifier, rotations, cov3D_precomp,
                       viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, kernel_size, subpixel_offset, prefiltered, debug, out_color, radii, device)
-    keep = []
-    if sh_tone is not None:
-        tone, k = _tone_block(sh_tone, device, P)
-        keep += [tone, k]
-        a.tone = C.pointer(tone)
-    out_color2 = torch.empty((3, H, W), dtype=torch.float32, device=device) if two else None
-    if sh_second is not None:
-        tone2, k = _tone_block(sh_second, device, P)
-        second = _SecondImage(None, out_color2.data_ptr(), None, None)
-        keep += [tone2, k, second]
-        a.tone2, a.sh_second, a.second = C.pointer(tone2), 1, C.pointer(second)
-    elif colors2 is not None:
-        colors2 = _f32(colors2, device)
-        second = _SecondImage(colors2.data_ptr(), out_color2.data_ptr(), None, None)
-        keep += [colors2, second]
-        a.second = C.pointer(second)
-    if filter_3D is not None:
-        filter_3D = _f32(filter_3D, device)
-        rawg = _RawGaussians(filter_3D.data_ptr(), None)
-        keep += [filter_3D, rawg]
-        a.raw = C.pointer(rawg)
-    if binning_capacity is not None:
-        if int(binning_capacity) <= 0:
-            raise RuntimeError("binning_capacity must be positive")
-        a.binning_capacity = int(binning_capacity)
-    ob = _options_block(opts)
-    a.options = C.pointer(ob)
+    keep = _attach_blocks(a, opts,  # noqa: F841  (alive until the call has returned)
+                          tone=None if sh_tone is None else _tone_block(sh_tone, device, P),
+                          tone2=None if sh_second is None else _tone_block(sh_second, device, P),
+                          second=_second_block(device, colors2=colors2, out_color2=out_color2) if two else None,
+                          raw=None if filter_3D is None else _raw_block(device, filter_3D))
+    a.binning_capacity = int(binning_capacity or 0)
     try:
         with torch.cuda.device(device):
             rendered = _lib.wg_rasterize_forward_ex(C.byref(a))
@@ -525,100 +561,67 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         alive = {t.ident for t in threading.enumerate()}
         for ident in [i for i in states if i not in alive]:
             states.pop(ident, None)
-    if sh_second is not None and dL_dout_color2 is None:
+    if sh_second is not None and dL_dout_color2 is None:   # the three mode checks, in front of both bindings
         raise RuntimeError("sh_second needs the second image's cotangent (dL_dout_color2)")
     record = bool(opts[2] or opts[1])
     dual = dL_dout_color2 is not None and sh_second is None
-    P = means3D.size(0)
-    if raw is not None and (len(raw) != 2 or raw[0].numel() != P or raw[1].numel() != P):
-        raise RuntimeError("raw = (filter_3D, raw_opacities) must have P elements each")
     if raw is not None and (not record or dual):
         raise RuntimeError("the raw-parameter backward pass needs grad_record = 1 and cannot be combined with the two-colour call")
-    if (dual or sh_second is not None) and ((dual and sh_tone is not None) or (not record and P != 0)):
+    if (dual or sh_second is not None) and ((dual and sh_tone is not None) or (not record and means3D.size(0) != 0)):
         raise RuntimeError("the two-colour backward pass needs the gradient record (grad_record = 1 or deterministic_backward = 1) and no sh_tone")
     if _torch_ext is not None:
         return _torch_ext.rasterize_gaussians_backward_ex(background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
                                                           viewmatrix, projmatrix, float(tan_fovx), float(tan_fovy), float(kernel_size), subpixel_offset,
                                                           dL_dout_color, sh, int(degree), campos, geomBuffer, int(R), binningBuffer, imageBuffer,
                                                           bool(debug), sh_tone, dL_dout_color2, raw, sh_second, opts)
-    device = means3D.device
-    H, W = dL_dout_color.size(1), dL_dout_color.size(2)
+    _check_backward_arguments(means3D, radii, colors, scales, rotations, cov3D_precomp, sh, dL_dout_color, sh_tone, dL_dout_color2, raw, sh_second)
+    return _backward_ctypes(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
+                            tan_fovy, kernel_size, subpixel_offset, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug,
+                            sh_tone, dL_dout_color2, raw, sh_second, opts)
+
+
+def _backward_ctypes(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
+                     kernel_size, subpixel_offset, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, sh_tone,
+                     dL_dout_color2, raw, sh_second, opts):
+    """The checked backward call through ctypes -> the reference's eight, + what the optional blocks add."""
+    device, P, H, W = means3D.device, means3D.size(0), dL_dout_color.size(1), dL_dout_color.size(2)
     sh = _f32(sh, device)
     M = sh.size(1) if sh.numel() != 0 else 0
-
+    dual = dL_dout_color2 is not None and sh_second is None
     # The reference zero-fills nine gradient tensors per call (rasterize_points.cu:157-165).  With the gradient record (the default,
     # include/wg_rasterizer.h) the library clears its own accumulator and every output is fully written by the per-Gaussian kernel
     # (zeros for culled Gaussians); without it the four accumulation targets of the per-tile pass share one zeroed allocation.
-    record = P != 0 and record
-    if record:
+    f = dict(dtype=torch.float32, device=device)
+    if P != 0 and (opts[2] or opts[1]):
         dL_dconic = None   # the reference's intermediate: not returned (rasterize_points.cu:201), so not requested
-        dL_dmeans2D = torch.empty((P, 3), dtype=torch.float32, device=device)
-        dL_dopacity = torch.empty((P, 1), dtype=torch.float32, device=device)
-        dL_dcolors = torch.empty((P, 3), dtype=torch.float32, device=device)
+        dL_dmeans2D, dL_dopacity, dL_dcolors = torch.empty((P, 3), **f), torch.empty((P, 1), **f), torch.empty((P, 3), **f)
     else:
-        acc = torch.zeros((P * 11,), dtype=torch.float32, device=device)
-        dL_dconic = acc[0:4 * P].view(P, 2, 2)
-        dL_dmeans2D = acc[4 * P:7 * P].view(P, 3)
-        dL_dcolors = acc[7 * P:10 * P].view(P, 3)
-        dL_dopacity = acc[10 * P:11 * P].view(P, 1)
-    have_scales = scales.numel() != 0
+        acc = torch.zeros((P * 11,), **f)
+        dL_dconic, dL_dmeans2D = acc[0:4 * P].view(P, 2, 2), acc[4 * P:7 * P].view(P, 3)
+        dL_dcolors, dL_dopacity = acc[7 * P:10 * P].view(P, 3), acc[10 * P:11 * P].view(P, 1)
     alloc = torch.empty if P != 0 else torch.zeros
-    dL_dmeans3D = alloc((P, 3), dtype=torch.float32, device=device)
-    dL_dcov3D = alloc((P, 6), dtype=torch.float32, device=device)
-    dL_dsh = alloc((P, M, 3), dtype=torch.float32, device=device)
-    dL_dscales = (alloc if have_scales else torch.zeros)((P, 3), dtype=torch.float32, device=device)
-    dL_drotations = (alloc if have_scales else torch.zeros)((P, 4), dtype=torch.float32, device=device)
-    dL_dcolors2 = alloc((P, 3), dtype=torch.float32, device=device) if dual else None
-    tone_grads = None
-    if sh_tone is not None:
-        tone_grads = tuple(None if v is None else alloc((P, 3), dtype=torch.float32, device=device) for v in sh_tone[:2])
-    tone2_grads = None
-    if sh_second is not None:
-        tone2_grads = tuple(None if v is None else alloc((P, 3), dtype=torch.float32, device=device) for v in sh_second[:2])
-
+    dL_dmeans3D, dL_dcov3D, dL_dsh = alloc((P, 3), **f), alloc((P, 6), **f), alloc((P, M, 3), **f)
+    alloc_sr = alloc if scales.numel() != 0 else torch.zeros
+    dL_dscales, dL_drotations = alloc_sr((P, 3), **f), alloc_sr((P, 4), **f)
+    dL_dcolors2 = alloc((P, 3), **f) if dual else None
+    tone_grads, tone2_grads = (None if t is None else tuple(None if v is None else alloc((P, 3), **f) for v in t[:2]) for t in (sh_tone, sh_second))
     if P != 0:
-        means3D = _f32(means3D, device)
-        background, colors = _f32(background, device), _f32(colors, device)
-        scales, rotations, cov3D_precomp = _f32(scales, device), _f32(rotations, device), _f32(cov3D_precomp, device)
-        viewmatrix, projmatrix, campos = _f32(viewmatrix, device), _f32(projmatrix, device), _f32(campos, device)
-        subpixel_offset = None if subpixel_offset is None else _f32(subpixel_offset, device)
-        dL_dout_color = _f32(dL_dout_color, device)
-        radii = radii if radii.is_contiguous() else radii.contiguous()
+        means3D, background, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, subpixel_offset, dL_dout_color = _f32s(
+            device, means3D, background, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, subpixel_offset, dL_dout_color)
+        radii = radii.contiguous()
         a = _BackwardArgs()
-        a.struct_size = C.sizeof(_BackwardArgs)
-        a.P, a.D, a.M, a.R, a.width, a.height, a.debug = P, int(degree), M, int(R), W, H, int(bool(debug))
-        a.scale_modifier, a.tan_fovx, a.tan_fovy, a.kernel_size = float(scale_modifier), float(tan_fovx), float(tan_fovy), float(kernel_size)
-        for name, t in (("background", background), ("means3D", means3D), ("shs", sh), ("colors_precomp", colors), ("scales", scales),
-                        ("rotations", rotations), ("cov3D_precomp", cov3D_precomp), ("viewmatrix", viewmatrix), ("projmatrix", projmatrix),
-                        ("campos", campos), ("subpixel_offset", subpixel_offset), ("radii", radii), ("dL_dpix", dL_dout_color), ("dL_dsh", dL_dsh)):
-            setattr(a, name, None if t is None else _ptr(t))
-        a.geom_buffer, a.binning_buffer, a.image_buffer = geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr()
-        a.dL_dmean2D, a.dL_dconic = dL_dmeans2D.data_ptr(), None if dL_dconic is None else dL_dconic.data_ptr()
-        a.dL_dopacity, a.dL_dcolor, a.dL_dmean3D, a.dL_dcov3D = dL_dopacity.data_ptr(), dL_dcolors.data_ptr(), dL_dmeans3D.data_ptr(), dL_dcov3D.data_ptr()
-        a.dL_dscale, a.dL_drot, a.stream = dL_dscales.data_ptr(), dL_drotations.data_ptr(), _stream(device)
-        keep = []
-        if sh_tone is not None:
-            tone, k = _tone_block(sh_tone, device, P, tone_grads)
-            keep += [tone, k]
-            a.tone = C.pointer(tone)
-        if sh_second is not None:
-            dL2 = _f32(dL_dout_color2, device)
-            tone2, k = _tone_block(sh_second, device, P, tone2_grads)
-            second = _SecondImage(None, None, dL2.data_ptr(), None)
-            keep += [dL2, tone2, k, second]
-            a.tone2, a.sh_second, a.second = C.pointer(tone2), 1, C.pointer(second)
-        elif dual:
-            dL2 = _f32(dL_dout_color2, device)
-            second = _SecondImage(None, None, dL2.data_ptr(), dL_dcolors2.data_ptr())
-            keep += [dL2, second]
-            a.second = C.pointer(second)
-        if raw is not None:
-            f3d, rop = _f32(raw[0], device), _f32(raw[1], device)
-            rawg = _RawGaussians(f3d.data_ptr(), rop.data_ptr())
-            keep += [f3d, rop, rawg]
-            a.raw = C.pointer(rawg)
-        ob = _options_block(opts)
-        a.options = C.pointer(ob)
+        _fill(a, device, P, degree, M, H, W, debug, scale_modifier, tan_fovx, tan_fovy, kernel_size, background=background, means3D=means3D, shs=sh,
+              colors_precomp=colors, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, viewmatrix=viewmatrix, projmatrix=projmatrix,
+              campos=campos, subpixel_offset=subpixel_offset, radii=radii, dL_dpix=dL_dout_color,
+              geom_buffer=geomBuffer, binning_buffer=binningBuffer, image_buffer=imageBuffer, dL_dmean2D=dL_dmeans2D, dL_dconic=dL_dconic,
+              dL_dopacity=dL_dopacity, dL_dcolor=dL_dcolors, dL_dmean3D=dL_dmeans3D, dL_dcov3D=dL_dcov3D, dL_dsh=dL_dsh, dL_dscale=dL_dscales,
+              dL_drot=dL_drotations)
+        a.R = int(R)
+        keep = _attach_blocks(a, opts,  # noqa: F841  (alive until the call has returned)
+                              tone=None if sh_tone is None else _tone_block(sh_tone, device, P, tone_grads),
+                              tone2=None if sh_second is None else _tone_block(sh_second, device, P, tone2_grads),
+                              second=None if dL_dout_color2 is None else _second_block(device, dL_dpix2=dL_dout_color2, dL_dcolor2=dL_dcolors2),
+                              raw=None if raw is None else _raw_block(device, *raw))
         with torch.cuda.device(device):
             status = _lib.wg_rasterize_backward_ex(C.byref(a))
         _check(status, "wg_rasterize_backward")
@@ -706,10 +709,6 @@ def view_image(imageBuffer, H, W):
                 order_fwd=_from_ptr(v.order_fwd, (tiles,), torch.int32, imageBuffer),
                 order_key=_from_ptr(v.order_key, (4,), torch.int32, imageBuffer),
                 order_bwd=_from_ptr(v.order_bwd, (tiles,), torch.int32, imageBuffer))
-
-
-_lib.wg_set_option.restype = _i
-_lib.wg_set_option.argtypes = [C.c_char_p, _i]
 
 
 _geometry_reuse_on = False   # the option "geometry_reuse" is read by this binding only: kept here too, so that no call has to ask the library
