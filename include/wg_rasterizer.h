@@ -191,6 +191,13 @@ typedef struct wg_backward_args {
     const wg_second_image* second;
     const wg_raw_gaussians* raw;
     const wg_call_options* options;
+    int colour_gradients_only;         /* 1: ONLY dL_dcolor [P,3] is computed (overwritten; zeros for Gaussians without instances) -- frames whose
+                                          geometry is frozen and whose colours alone take a gradient.  One front-to-back walk that sums the
+                                          forward pass's blend weights times dL_dpix; no per-Gaussian pass.  Needs colors_precomp-mode (shs NULL),
+                                          dL_dcolor, dL_dpix, background and the three buffers; every other output pointer may be NULL and is
+                                          never written; the grad_record option is ignored.  WG_ERR_INVALID_ARGUMENT with shs, tone, tone2,
+                                          sh_second, second, raw, or deterministic_backward = 1.  Absent (a struct of version 0.5's 312
+                                          bytes) = 0 = the full backward pass. */
 } wg_backward_args;
 
 int wg_rasterize_forward_ex(const wg_forward_args* args);

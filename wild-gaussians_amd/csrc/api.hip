@@ -670,6 +670,7 @@ int remembered_mode(const char* image_buffer) {
 static int forward_impl(const wg_forward_args& a);
 static int recolor_impl(const wg_forward_args& a);
 static int backward_impl(const wg_backward_args& a);
+static int backward_colour_impl(const wg_backward_args& a, const wg::Options& opt);
 
 int wg_rasterize_forward(wg_alloc_fn geometry_alloc, void* geometry_user, wg_alloc_fn binning_alloc, void* binning_user,
                          wg_alloc_fn image_alloc, void* image_user, int P, int D, int M, const float* background, int width,
@@ -1124,6 +1125,7 @@ static int backward_impl(const wg_backward_args& a) {
         const int fwd_mode = remembered_mode(image_buffer);
         if (fwd_mode >= 0 && fwd_mode != (opt.exact_compositing ? 1 : 0)) return WG_ERR_INVALID_ARGUMENT;
     }
+    if (a.colour_gradients_only != 0) return backward_colour_impl(a, opt);
     // two colour sets over one walk: the thirteen sums go to the gradient record (or, deterministic mode, to fourteen-float slots)
     const bool dual = second != nullptr && P > 0;
     // raw-parameter mode: the per-Gaussian kernel turns the gradients of the activated values into those of the raw parameters where it
@@ -1238,6 +1240,47 @@ static int backward_impl(const wg_backward_args& a) {
     {
         hipError_t e = det_guard.release();
         if (e != hipSuccess) return hip_fail(e, "deterministic backward scratch release");
+    }
+    return WG_OK;
+}
+
+// wg_backward_args::colour_gradients_only: dL_dcolor alone, from one front-to-back walk over the frame's lists (render_bwd.hip: render_backward_colour_kernel).
+// Called by backward_impl once the frame's exact_compositing has been matched against the call's.  Nothing is recorded (grad_record is
+// ignored), no scratch is leased, no per-Gaussian kernel follows: the call captures in a hipGraph like the atomic mode of the full pass.
+static int backward_colour_impl(const wg_backward_args& a, const wg::Options& opt) {
+    hipStream_t stream = reinterpret_cast<hipStream_t>(a.stream);
+    const int P = a.P, R = a.R, width = a.width, height = a.height, debug = a.debug;
+    // SH colours, tones, a second image and raw parameters have per-Gaussian work behind dL_dcolor; a slot path for three sums does not exist
+    if (a.shs || a.tone || a.tone2 || a.sh_second || a.second || a.raw || opt.deterministic_backward) return WG_ERR_INVALID_ARGUMENT;
+    if (a.image_buffer != nullptr) {   // a deferred forward call's verdict, as in the full pass
+        const int verdict = check_ticket(image_key(a.image_buffer), stream);
+        if (verdict != WG_OK) return verdict;
+    }
+    if (P < 0 || R < 0 || width <= 0 || height <= 0) return WG_ERR_INVALID_ARGUMENT;
+    if (P == 0) return WG_OK;
+    if (!a.geom_buffer || !a.binning_buffer || !a.image_buffer || !a.dL_dpix || !a.background || !a.dL_dcolor) return WG_ERR_INVALID_ARGUMENT;
+
+    const int gx = (width + wg::TILE_X - 1) / wg::TILE_X, gy = (height + wg::TILE_Y - 1) / wg::TILE_Y;
+    char *geom_buffer = a.geom_buffer, *binning_buffer = a.binning_buffer, *image_buffer = a.image_buffer;   // (fromChunk advances its argument)
+    wg::GeometryState geom = wg::GeometryState::fromChunk(geom_buffer, (size_t)P, false);
+    wg::BinningState bin = wg::BinningState::fromChunk(binning_buffer, (size_t)R, false);  // only point_list is used
+    wg::ImageState img = wg::ImageState::fromChunk(image_buffer, (size_t)width * height, (size_t)gx * gy);
+
+    // dL_dcolor is an output: cleared here.  The launch that orders the tiles clears whole float4s of a 16-byte aligned array on the side; what
+    // that leaves -- the last (3 P) % 4 floats, an unaligned array, a frame without instances -- takes a memset.
+    const size_t floats = (size_t)P * 3;
+    const bool side_clear = R > 0 && (reinterpret_cast<uintptr_t>(a.dL_dcolor) & 15u) == 0 && floats >= 4;
+    const size_t side_floats = side_clear ? (floats & ~(size_t)3) : 0;
+    if (side_floats < floats) {
+        StageScope scope_(WG_STAGE_RENDER_BACKWARD, stream);
+        hipError_t e = hipMemsetAsync(a.dL_dcolor + side_floats, 0, (floats - side_floats) * sizeof(float), stream);
+        if (e != hipSuccess) return hip_fail(e, "dL_dcolor memset");
+    }
+    if (R > 0) {
+        WG_STAGE(WG_STAGE_RENDER_BACKWARD, wg::launch_tile_order(img.tile_last, nullptr, img.order_bwd, gx * gy, side_clear ? a.dL_dcolor : nullptr, side_floats,
+                                                                 opt.backward_order_period, stream), "tile_order");
+        WG_STAGE(WG_STAGE_RENDER_BACKWARD, wg::launch_render_backward_colour(width, height, gx, gy, img, bin, geom, a.subpixel_offset, a.dL_dpix, a.dL_dcolor,
+                                                                             opt.exact_compositing != 0, stream), "render_backward_colour");
     }
     return WG_OK;
 }

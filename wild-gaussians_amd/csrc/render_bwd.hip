@@ -117,6 +117,18 @@ __device__ __forceinline__ float butterfly13(float v0, float v1, float v2, float
     return y;
 }
 
+// Three per-lane values summed over the wave: on return every lane of row 0 (lanes 0 - 15) holds the total of v0, of row 2 that of v1, of
+// rows 1 and 3 that of v2.
+__device__ __forceinline__ float butterfly3(float v0, float v1, float v2) {
+    const float w0 = pair_x32(v0, v1), w1 = pair_x32(v2, v2);   // xor 32: lanes 0 - 31 v0, lanes 32 - 63 v1; v2 in both halves
+    float y = pair_x16(w0, w1);                                  // xor 16: even rows w0, odd rows w1
+    y += dpp_f<0xB1>(y);    // quad_perm [1,0,3,2]
+    y += dpp_f<0x4E>(y);    // quad_perm [2,3,0,1]
+    y += dpp_f<0x124>(y);   // row_ror 4
+    y += dpp_f<0x128>(y);   // row_ror 8
+    return y;
+}
+
 // RECORD (default, wg_set_option("grad_record")): the ten reduced values of an instance go, unscaled, to ONE 48-byte gradient
 // record of its Gaussian (grad_rec[12 id + k], k = the value's index; wg_common.h: GRAD_REC_*) -- one L2 line per instance (two for
 // a quarter of the records) instead of partial lines of four arrays, and the per-Gaussian factors (opacity, 0.5 W,
@@ -667,6 +679,170 @@ hipError_t launch_render_backward(int W, int H, int gx, int gy, const ImageState
 #undef WG_LAUNCH
 #undef WG_LAUNCH2
 #undef WG_LAUNCH3
+    return hipGetLastError();
+}
+
+// ---- K9c: the colour-only backward pass (wg_backward_args::colour_gradients_only) -----------------------------------------------------------
+//     dL_dcolor[g, c] = sum over the (pixel, Gaussian) pairs the forward pass blended of  alpha * T * dL_dpixel[c]
+//
+// alpha * T is the forward pass's own blend weight, so this is the FORWARD walk (render_fwd.hip: fwd_walk) run again -- front to back, T
+// carried per pixel, alpha from the forward kernel's evaluator, the same strip masks -- with the colour sums replaced by three per-instance
+// sums of w * dL_dpixel.  It needs no conic, mean or opacity derivative, no T / (1 - alpha) reconstruction and no per-Gaussian kernel behind
+// it; the splat record's colours are not even read.  What bounds the walk:
+//   * the tile's list only up to tile_last[tile], the last position any of its pixels blended (what render_backward_kernel starts from): the
+//     unsorted tails of lazily sorted lists and the far instances no tile asked for are never read;
+//   * a pixel takes part while the list position is below its stored n_contrib.  Such a pixel was still accumulating in the forward pass and
+//     did not stop there (the instance a pixel stops at is not blended and lies behind its last contributor), so "blended" is exactly
+//     "passes the two skips" -- taken on eval_alpha_exact_values (EXACT) or eval_alpha_values, the forward kernel's own: the decisions are
+//     the forward's by construction, with no error band to re-evaluate, and T is the forward's bit for bit.
+// Per instance with a contributing pixel the three sums are reduced over the wave and lanes 0, 32 and 16 add red, green and blue to
+// dL_dcolor[3 id + c] with one float atomic each; an instance without a contributing lane issues nothing.
+// The reduction is a butterfly on pair_x32 / pair_x16 / dpp_f above.  render_backward_kernel measured, for ITS ten sums, that parking the five values
+// the first stage leaves in LDS beats the rest of the butterfly (WG_BWD_LDS_REDUCE).  Three sums leave TWO values behind the first stage:
+// the rest of the butterfly is one swap-add and four DPP adds, against two LDS writes, eight reads, seven adds and two DPP adds for the LDS
+// form -- so the butterfly was chosen, by instruction count; no A/B of the two forms was taken for this kernel.
+template <bool EXACT>
+__global__ void __launch_bounds__(64) render_backward_colour_kernel(
+    int W, int H, int gx, int tiles, const uint32_t* __restrict__ order, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
+    const float4* __restrict__ splats, const float2* __restrict__ subpixel_offset, const uint32_t* __restrict__ n_contrib,
+    const uint32_t* __restrict__ tile_last, const float* __restrict__ dL_dpix, float* __restrict__ dL_dcolor) {
+    __shared__ float4 lds[BATCH * 2];   // r0 = (mx, my, conic terms), r1 = (conic term, opacity, byte offset of the Gaussian's gradient, -)
+
+    const int tile = (int)order[xcd_tile(blockIdx.x, tiles)];
+    const uint2 range = ranges[tile];
+    const int n = min((int)tile_last[tile], (int)(range.y - range.x));   // (tile_last never exceeds the list: the min only guards the reads)
+    if (n <= 0) return;
+    const int lane = threadIdx.x;
+    const int tx = tile % gx, ty = tile / gx;
+    const size_t plane = (size_t)W * H;
+
+    float pfx[4], pfy[4], T[4], dLr[4], dLg[4], dLb[4];
+    int last[4];
+    StripBounds sb;
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const int px = tx * TILE_X + strip_x(lane, s), py = ty * TILE_Y + strip_y(lane, s);
+        const bool inside = px < W && py < H;
+        float2 off = make_float2(0.f, 0.f);
+        T[s] = 1.0f; last[s] = 0; dLr[s] = dLg[s] = dLb[s] = 0.f;
+        if (inside) {
+            const size_t pix = (size_t)W * py + px;
+            if (subpixel_offset) off = subpixel_offset[pix];
+            last[s] = (int)n_contrib[pix];
+            dLr[s] = dL_dpix[pix];
+            dLg[s] = dL_dpix[plane + pix];
+            dLb[s] = dL_dpix[2 * plane + pix];
+        }
+        pfx[s] = (float)px + off.x;
+        pfy[s] = (float)py + off.y;
+        const float inf = __builtin_huge_valf();
+        sb.x0[s] = wave_min_uniform(inside ? pfx[s] : inf);
+        sb.x1[s] = wave_max_uniform(inside ? pfx[s] : -inf);
+        sb.y0[s] = wave_min_uniform(inside ? pfy[s] : inf);
+        sb.y1[s] = wave_max_uniform(inside ? pfy[s] : -inf);
+    }
+    // the last list position any pixel of a strip blended (wave-uniform): behind it the strip receives nothing
+    int strip_last[4];
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        int m = last[s];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) m = max(m, __shfl_xor(m, d));
+        strip_last[s] = __builtin_amdgcn_readfirstlane(m);
+    }
+
+    // after butterfly3(): lane 0 holds red, lane 32 green, lane 16 blue (lane 48: a copy of blue, not issued)
+    const bool issue = (lane & 15) == 0 && lane != 48;
+    const uint32_t chan_bytes = lane == 0 ? 0u : (lane == 32 ? 4u : 8u);
+
+    // Records travel list -> registers -> LDS one batch ahead of the walk, their ids two batches ahead, indices clamped to the walked part of
+    // the list instead of predicated (render_fwd.hip: fwd_walk).  Nothing at or behind position n is read.
+    const uint32_t* list = point_list + range.x;
+    const int nl = n - 1;
+    uint32_t id_cur = list[min(lane, nl)];
+    float4 a0 = splats[3 * (size_t)id_cur], a1 = splats[3 * (size_t)id_cur + 1], a2 = splats[3 * (size_t)id_cur + 2];
+    uint32_t id_next = list[min(BATCH + lane, nl)];
+    float acr = 0.f, acg = 0.f, acb = 0.f;   // cleared after each reduction only: an instance nobody contributed to leaves them at zero
+
+    for (int base = 0; base < n; base += BATCH) {
+        const int cnt = min(BATCH, n - base);
+        float4 s0 = a0, s1 = a1;
+        const uint32_t mymask = lane < cnt ? strip_mask(s0, s1, a2, sb) : 0u;
+        __syncthreads();   // (the workgroup is the wave: no s_barrier; see fwd_walk on why it is kept)
+        if (EXACT) halve_conic(s0, s1); else scale_conic(s0, s1);
+        s1.z = __uint_as_float(id_cur * (uint32_t)(3 * sizeof(float)));   // 12 P < 2^32, as render_bwd.hip assumes of 48 P
+        lds[2 * lane] = s0;
+        lds[2 * lane + 1] = s1;
+        __syncthreads();
+        {
+            id_cur = id_next;
+            const size_t r = 3 * (size_t)id_next;
+            a0 = splats[r];
+            a1 = splats[r + 1];
+            a2 = splats[r + 2];
+            id_next = list[min(base + 2 * BATCH + lane, nl)];
+        }
+        // instance j of the batch sits at position base + j: strip s can still receive from it while base + j < strip_last[s]
+        uint64_t reach[4];
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            const int live_n = strip_last[s] - base;   // wave-uniform
+            const uint64_t live = live_n >= 64 ? ~0ull : (live_n <= 0 ? 0ull : ((1ull << live_n) - 1ull));
+            reach[s] = __ballot((mymask >> s) & 1u) & live;
+        }
+        uint64_t todo = reach[0] | reach[1] | reach[2] | reach[3];
+        while (todo != 0ull) {
+            const int j = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const float4 r0 = lds[2 * j];
+            const float4 r1 = lds[2 * j + 1];
+            const SplatCoef sc = coef_of(r0, r1);
+            const ExactCoef xc = exact_coef_of(r0, r1);
+            const int pos = base + j;
+            uint64_t any_m = 0ull;
+#pragma unroll
+            for (int s = 0; s < 4; s++) {
+                if (((reach[s] >> j) & 1ull) == 0ull) continue;   // wave-uniform
+                const uint64_t in_m = __builtin_amdgcn_ballot_w64(pos < last[s]);
+                float alpha;
+                uint64_t pass_m;
+                if (EXACT) {
+                    float dx, dy, G;
+                    const float power = eval_alpha_exact_values(xc, pfx[s], pfy[s], dx, dy, G, alpha);
+                    pass_m = __builtin_amdgcn_ballot_w64(!(power > 0.0f)) & __builtin_amdgcn_ballot_w64(!(alpha < (1.0f / 255.0f)));
+                } else {
+                    PairEval e;
+                    const float p2 = eval_alpha_values(sc, pfx[s], pfy[s], e);
+                    alpha = e.alpha;
+                    pass_m = __builtin_amdgcn_ballot_w64(!(p2 > 0.0f)) & __builtin_amdgcn_ballot_w64(!(alpha < (1.0f / 255.0f)));
+                }
+                const uint64_t go_m = in_m & pass_m;
+                any_m |= go_m;
+                if (__builtin_amdgcn_inverse_ballot_w64(go_m)) {
+                    const float w = alpha * T[s];
+                    acr += w * dLr[s];
+                    acg += w * dLg[s];
+                    acb += w * dLb[s];
+                    T[s] = EXACT ? ref_test_T(T[s], alpha) : T[s] - w;   // as fwd_walk carries it
+                }
+            }
+            if (any_m == 0ull) continue;
+            const float total = butterfly3(acr, acg, acb);
+            if (issue) unsafeAtomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(dL_dcolor) + (size_t)(__float_as_uint(r1.z) + chan_bytes)), total);
+            acr = acg = acb = 0.f;
+        }
+    }
+}
+
+hipError_t launch_render_backward_colour(int W, int H, int gx, int gy, const ImageState& img, const BinningState& b, const GeometryState& g,
+                                         const float* subpixel_offset, const float* dL_dpix, float* dL_dcolor, bool exact, hipStream_t stream) {
+    const int tiles = gx * gy;
+    if (tiles <= 0) return hipSuccess;
+#define WG_LAUNCH(EX)                                                                                                                         \
+    hipLaunchKernelGGL(render_backward_colour_kernel<EX>, dim3(tiles), dim3(64), 0, stream, W, H, gx, tiles, img.order_bwd, img.ranges,         \
+                       b.point_list, g.splats, reinterpret_cast<const float2*>(subpixel_offset), img.n_contrib, img.tile_last, dL_dpix, dL_dcolor)
+    if (exact) WG_LAUNCH(true); else WG_LAUNCH(false);
+#undef WG_LAUNCH
     return hipGetLastError();
 }
 

@@ -207,7 +207,7 @@ struct Gradients {
 
 Gradients backward(const Scene& s, const torch::Tensor& radii, const torch::Tensor& dL_dout_color, const torch::Tensor& geomBuffer, const int R,
                    const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const py::object& sh_tone, const OptTensor& dL_dout_color2,
-                   const py::object& raw_in, const py::object& sh_second, const wg_call_options& co) {
+                   const py::object& raw_in, const py::object& sh_second, const wg_call_options& co, const bool colour_only = false) {
     const auto dev = s.means3D.device();
     const c10::DeviceGuard guard(dev);
     const int P = static_cast<int>(s.means3D.size(0));
@@ -240,6 +240,26 @@ Gradients backward(const Scene& s, const torch::Tensor& radii, const torch::Tens
     // every one of them is fully written by the library (zeros for culled Gaussians), without it the four accumulation targets (one of
     // them dL_dconic, the reference's intermediate: not returned, so not requested with the record) must arrive zeroed.
     const auto f = s.means3D.options().dtype(torch::kFloat32);
+    if (colour_only) {   // wg_backward_args::colour_gradients_only: dL_dcolors alone exists, and the library fills it
+        Gradients g;
+        g.colors = P != 0 ? torch::empty({P, 3}, f) : torch::zeros({P, 3}, f);
+        if (P == 0) return g;
+        const auto dL = f32(dL_dout_color, dev);
+        wg_backward_args a{};
+        in.fill(a, s, H, W, &wg_backward_args::campos, co, dev);
+        a.R = R;
+        a.geom_buffer = bytes_of(geomBuffer); a.binning_buffer = bytes_of(binningBuffer); a.image_buffer = bytes_of(imageBuffer);
+        a.dL_dpix = ptr(dL);
+        a.dL_dcolor = g.colors.data_ptr<float>();
+        a.colour_gradients_only = 1;
+        int status;
+        {
+            py::gil_scoped_release nogil;
+            status = wg_rasterize_backward_ex(&a);
+        }
+        check(status, "wg_rasterize_backward");
+        return g;
+    }
     const bool record = P != 0 && (co.grad_record != 0 || co.deterministic_backward != 0), have_scales = s.scales.numel() != 0;
     auto alloc = [&](std::initializer_list<int64_t> shape, bool written) {
         return (P != 0 && written) ? torch::empty(shape, f) : torch::zeros(shape, f);
@@ -378,10 +398,27 @@ py::tuple RasterizeGaussiansBackwardEx(const torch::Tensor& background, const to
     return py::tuple(out);
 }
 
+// the colour-only backward pass (wg_backward_args::colour_gradients_only; _C.py refuses the calls it does not serve in front of both
+// bindings) -> the reference's eight places, dL_dcolors alone filled
+py::tuple RasterizeGaussiansBackwardColour(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& colors,
+                                           const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier,
+                                           const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix,
+                                           const float tan_fovx, const float tan_fovy, const float kernel_size, const OptTensor& subpixel_offset,
+                                           const torch::Tensor& dL_dout_color, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
+                                           const torch::Tensor& geomBuffer, const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
+                                           const bool debug, const std::tuple<int, int, int>& options) {
+    const py::object none = py::none();
+    const Scene s{background, means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, kernel_size,
+                  opt(subpixel_offset), sh, degree, campos, debug};
+    const Gradients g = backward(s, radii, dL_dout_color, geomBuffer, R, binningBuffer, imageBuffer, none, c10::nullopt, none, none, call_options(options), true);
+    return py::make_tuple(py::none(), g.colors, py::none(), py::none(), py::none(), py::none(), py::none(), py::none());
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {   // ext.cpp:15-19
     m.def("rasterize_gaussians", &RasterizeGaussiansHIP);
     m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackwardHIP);
     m.def("mark_visible", &markVisible);
     m.def("rasterize_gaussians_ex", &RasterizeGaussiansEx);                    // + the blocks of wg_forward_args
     m.def("rasterize_gaussians_backward_ex", &RasterizeGaussiansBackwardEx);   // + the blocks of wg_backward_args
+    m.def("rasterize_gaussians_backward_colour", &RasterizeGaussiansBackwardColour);   // wg_backward_args::colour_gradients_only
 }

@@ -333,6 +333,10 @@ hipError_t launch_render_backward(int W, int H, int gx, int gy, const ImageState
                                   const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
                                   float* dL_dcolor, bool record, bool exact, const float* dL_dpix2, float* det_slots, unsigned char* det_flags, size_t slot_capacity, int P,
                                   hipStream_t stream);  // det_slots != nullptr: deterministic mode (det_flags: one byte per slot, cleared)
+// the colour-only backward pass (render_bwd.hip: render_backward_colour_kernel): dL_dcolor[3 P] += the forward pass's blend weights times dL_dpix, over each tile's
+// first tile_last entries in img.order_bwd's order; dL_dcolor must arrive cleared
+hipError_t launch_render_backward_colour(int W, int H, int gx, int gy, const ImageState& img, const BinningState& b, const GeometryState& g,
+                                         const float* subpixel_offset, const float* dL_dpix, float* dL_dcolor, bool exact, hipStream_t stream);
 
 struct BwdParams {
     int P, D, M, W, H;

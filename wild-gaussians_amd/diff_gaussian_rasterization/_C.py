@@ -414,6 +414,36 @@ def call_options(**kw):
         d.update(saved)
 
 
+# The colour-only backward pass (wg_backward_args::colour_gradients_only): a frame whose geometry is frozen and whose precomputed colours alone
+# take a gradient gets dL_dcolors from one cheap walk and nothing else.  The flag travels BESIDE the three per-call options (it selects what
+# is computed, not how): the `colour_gradients_only=` keyword of rasterize_gaussians_backward, else the calling thread's default, which
+# `colour_gradients_only(True)` sets for a `with` block (for callers that cannot pass keywords).
+COLOUR_ONLY_MSG = ("colour_gradients_only needs precomputed colours and nothing that has per-Gaussian work behind them "
+                   "(no SH colours, sh_tone, sh_second, second colour set or raw parameters) and deterministic_backward = 0")
+
+
+def resolve_colour_gradients_only(value=None) -> bool:
+    """`value` (the keyword; None = not given) over the calling thread's default."""
+    return bool(getattr(_tls, "colour_gradients_only", False) if value is None else value)
+
+
+@contextlib.contextmanager
+def colour_gradients_only(on=True):
+    """`with _C.colour_gradients_only(True): ...` -- the calling thread's default for the block."""
+    saved = getattr(_tls, "colour_gradients_only", False)
+    _tls.colour_gradients_only = bool(on)
+    try:
+        yield
+    finally:
+        _tls.colour_gradients_only = saved
+
+
+def colour_only_refused(has_sh, toned, second, raw, sh_second, opts) -> bool:
+    """What the colour-only backward pass refuses, each argument a bool but the resolved options (the library returns
+    WG_ERR_INVALID_ARGUMENT for the same calls)."""
+    return bool(has_sh or toned or second or raw or sh_second or opts[1])
+
+
 def _fill(a, device, P, degree, M, H, W, debug, scale_modifier, tan_fovx, tan_fovy, kernel_size, **tensors):
     """The fields wg_forward_args and wg_backward_args share; every other pointer field by name (None or zero-sized = NULL)."""
     a.struct_size = C.sizeof(a)
@@ -543,16 +573,20 @@ def _forward_ctypes(background, means3D, colors, opacity, scales, rotations, sca
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, kernel_size, subpixel_offset, dL_dout_color, sh,
                                  degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, sh_tone=None, dL_dout_color2=None, raw=None,
-                                 sh_second=None, options=None):
+                                 sh_second=None, options=None, colour_gradients_only=None):
     """The reference's `rasterize_gaussians_backward` (rasterize_points.h:42-66) -> the eight tensors, plus by keyword:
     sh_tone: two more tensors are appended, dL_dsh_mul, dL_dsh_offset (None where the input was None); dL_dsh is then the gradient of the raw
       coefficients.
     sh_second (a frame rasterized with sh_second; needs dL_dout_color2): the eight + (dL_dsh_mul, dL_dsh_offset, dL_dsh_mul2, dL_dsh_offset2).
     dL_dout_color2 (a frame rasterized with colors2): the second image's cotangent; the result ends with dL_dcolors2 [P,3].
     raw = (filter_3D, raw_opacities) of a raw-parameter forward call: dL_dopacity / dL_dscales / dL_drotations are the RAW parameters' gradients.
-    options: the frame's forward call's per-call options (resolve_call_options)."""
+    options: the frame's forward call's per-call options (resolve_call_options).
+    colour_gradients_only (None = the calling thread's default, off unless inside `with colour_gradients_only(True)`): only dL_dcolors [P,3]
+      is computed and allocated; the eight-tuple has None in the other seven places.  Precomputed colours only, no optional block, no
+      deterministic_backward."""
     global _reuse_epoch
     opts = resolve_call_options(options)
+    colour_only = resolve_colour_gradients_only(colour_gradients_only)
     _reuse_epoch += 1   # what the forward calls remembered ends here (see "Geometry reuse" above) ...
     states = _PerThread._states
     for st in list(states.values()):                     # ... and so do the references that kept those frames' scratch alive (any thread's)
@@ -561,7 +595,10 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         alive = {t.ident for t in threading.enumerate()}
         for ident in [i for i in states if i not in alive]:
             states.pop(ident, None)
-    if sh_second is not None and dL_dout_color2 is None:   # the three mode checks, in front of both bindings
+    if colour_only and colour_only_refused(sh.numel() != 0, sh_tone is not None, dL_dout_color2 is not None, raw is not None,
+                                           sh_second is not None, opts):   # the mode checks, in front of both bindings
+        raise RuntimeError(COLOUR_ONLY_MSG)
+    if sh_second is not None and dL_dout_color2 is None:
         raise RuntimeError("sh_second needs the second image's cotangent (dL_dout_color2)")
     record = bool(opts[2] or opts[1])
     dual = dL_dout_color2 is not None and sh_second is None
@@ -569,6 +606,14 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         raise RuntimeError("the raw-parameter backward pass needs grad_record = 1 and cannot be combined with the two-colour call")
     if (dual or sh_second is not None) and ((dual and sh_tone is not None) or (not record and means3D.size(0) != 0)):
         raise RuntimeError("the two-colour backward pass needs the gradient record (grad_record = 1 or deterministic_backward = 1) and no sh_tone")
+    if colour_only:
+        if _torch_ext is not None:
+            return _torch_ext.rasterize_gaussians_backward_colour(background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
+                                                                  viewmatrix, projmatrix, float(tan_fovx), float(tan_fovy), float(kernel_size),
+                                                                  subpixel_offset, dL_dout_color, sh, int(degree), campos, geomBuffer, int(R), binningBuffer,
+                                                                  imageBuffer, bool(debug), opts)
+        _check_backward_arguments(means3D, radii, colors, scales, rotations, cov3D_precomp, sh, dL_dout_color, None, None, None, None)
+        return _backward_colour_ctypes(background, means3D, colors, subpixel_offset, dL_dout_color, geomBuffer, R, binningBuffer, imageBuffer, debug, opts)
     if _torch_ext is not None:
         return _torch_ext.rasterize_gaussians_backward_ex(background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
                                                           viewmatrix, projmatrix, float(tan_fovx), float(tan_fovy), float(kernel_size), subpixel_offset,
@@ -631,6 +676,23 @@ def _backward_ctypes(background, means3D, radii, colors, scales, rotations, scal
     if dual:
         return out + (dL_dcolors2,)
     return out if sh_tone is None else out + tone_grads   # (raw-parameter mode: same tuple, slots 2, 6, 7 are gradients of the raw parameters)
+
+
+def _backward_colour_ctypes(background, means3D, colors, subpixel_offset, dL_dout_color, geomBuffer, R, binningBuffer, imageBuffer, debug, opts):
+    """The checked colour-only backward call through ctypes -> the reference's eight places, dL_dcolors alone filled."""
+    device, P, H, W = means3D.device, means3D.size(0), dL_dout_color.size(1), dL_dout_color.size(2)
+    dL_dcolors = (torch.empty if P != 0 else torch.zeros)((P, 3), dtype=torch.float32, device=device)   # the library fills it
+    if P != 0:
+        background, colors, subpixel_offset, dL_dout_color = _f32s(device, background, colors, subpixel_offset, dL_dout_color)
+        a = _BackwardArgs()
+        _fill(a, device, P, 0, 0, H, W, debug, 1.0, 1.0, 1.0, 0.0, background=background, colors_precomp=colors, subpixel_offset=subpixel_offset,
+              dL_dpix=dL_dout_color, geom_buffer=geomBuffer, binning_buffer=binningBuffer, image_buffer=imageBuffer, dL_dcolor=dL_dcolors)
+        a.R, a.colour_gradients_only = int(R), 1
+        keep = _attach_blocks(a, opts)  # noqa: F841  (alive until the call has returned)
+        with torch.cuda.device(device):
+            status = _lib.wg_rasterize_backward_ex(C.byref(a))
+        _check(status, "wg_rasterize_backward")
+    return (None, dL_dcolors, None, None, None, None, None, None)
 
 
 def forward_status(imageBuffer, H, W):

@@ -26,6 +26,7 @@ from . import _C
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians"]
 call_options = _C.call_options   # `with call_options(deterministic_backward=1): ...` (thread-local, scoped; see _C.py)
+colour_gradients_only = _C.colour_gradients_only   # `with colour_gradients_only(True): ...`: the colour-only backward pass as the thread's default
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -76,7 +77,8 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                 sh_mul=None, sh_offset=None, sh_pre_clamp_max=None, sh_post_clamp_max=None, binning_capacity=None, colors_precomp2=None,
-                filter_3D=None, sh_second=False, sh_mul2=None, sh_offset2=None, sh_pre_clamp_max2=None, sh_post_clamp_max2=None, call_options=None):
+                filter_3D=None, sh_second=False, sh_mul2=None, sh_offset2=None, sh_pre_clamp_max2=None, sh_post_clamp_max2=None, call_options=None,
+                colour_gradients_only=None):
         rs = raster_settings
         native_args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                        rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.kernel_size, rs.subpixel_offset,
@@ -86,6 +88,13 @@ class _RasterizeGaussians(torch.autograd.Function):
         # per-call options: resolved ONCE here (keyword > the calling thread's defaults) and carried to the backward call on ctx
         ctx.call_options = _C.resolve_call_options(call_options)
         extra = dict(options=ctx.call_options)
+        # the colour-only backward pass (wg_backward_args::colour_gradients_only): resolved ONCE here too (keyword > the calling thread's default);
+        # what it cannot serve is refused now, not in the middle of a backward pass
+        ctx.colour_only = _C.resolve_colour_gradients_only(colour_gradients_only)
+        toned = any(v is not None for v in (sh_mul, sh_offset, sh_pre_clamp_max, sh_post_clamp_max))
+        if ctx.colour_only and _C.colour_only_refused(sh.numel() != 0, toned, colors_precomp2 is not None, filter_3D is not None, bool(sh_second),
+                                                      ctx.call_options):
+            raise Exception(_C.COLOUR_ONLY_MSG)
         # per-Gaussian affine + clamps on the SH coefficients in-kernel (wg_sh_tone)
         ctx.sh_tone = None
         if sh_mul is not None or sh_offset is not None or sh_pre_clamp_max is not None or sh_post_clamp_max is not None:
@@ -148,7 +157,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         native_args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
                        rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.kernel_size, rs.subpixel_offset, grad_out_color, sh,
                        rs.sh_degree, rs.campos, geom_buf, ctx.num_rendered, binning_buf, img_buf, rs.debug)
-        extra = dict(options=ctx.call_options)   # the frame's forward call's
+        extra = dict(options=ctx.call_options, colour_gradients_only=ctx.colour_only)   # the frame's forward call's
+        if ctx.colour_only:   # dL_dcolors and nothing else: the geometry inputs' .grad stay as they were
+            g_colors = _call_native(lambda *a: _C.rasterize_gaussians_backward(*a, **extra), native_args, rs.debug, "snapshot_bw.dump", "backward")[1]
+            return (None, None, None, g_colors) + (None,) * 19
         if ctx.sh_tone is not None:
             extra["sh_tone"] = ctx.sh_tone
         if ctx.raw:
@@ -172,15 +184,17 @@ class _RasterizeGaussians(torch.autograd.Function):
             g_mul, g_offset = shaped(res[8], ctx.sh_tone[0]), shaped(res[9], ctx.sh_tone[1])
         # order of forward()'s inputs; None for raster_settings, the clamp constants and the options
         return (g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3Ds, None, g_mul, g_offset, None, None, None, g_colors2, None,
-                None, g_mul2, g_offset2, None, None, None)
+                None, g_mul2, g_offset2, None, None, None, None)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                         sh_mul=None, sh_offset=None, sh_pre_clamp_max=None, sh_post_clamp_max=None, binning_capacity=None, colors_precomp2=None,
-                        filter_3D=None, sh_second=False, sh_mul2=None, sh_offset2=None, sh_pre_clamp_max2=None, sh_post_clamp_max2=None, call_options=None):
+                        filter_3D=None, sh_second=False, sh_mul2=None, sh_offset2=None, sh_pre_clamp_max2=None, sh_post_clamp_max2=None, call_options=None,
+                        *, colour_gradients_only=None):
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                      raster_settings, sh_mul, sh_offset, sh_pre_clamp_max, sh_post_clamp_max, binning_capacity, colors_precomp2,
-                                     filter_3D, sh_second, sh_mul2, sh_offset2, sh_pre_clamp_max2, sh_post_clamp_max2, call_options)
+                                     filter_3D, sh_second, sh_mul2, sh_offset2, sh_pre_clamp_max2, sh_post_clamp_max2, call_options,
+                                     colour_gradients_only)
 
 
 class GaussianRasterizer(nn.Module):
@@ -203,8 +217,16 @@ class GaussianRasterizer(nn.Module):
                 filter_3D: Optional[torch.Tensor] = None, sh_second: bool = False, sh_mul2: Optional[torch.Tensor] = None,
                 sh_offset2: Optional[torch.Tensor] = None, sh_pre_clamp_max2: Optional[float] = None,
                 sh_post_clamp_max2: Optional[float] = None, exact_compositing: Optional[bool] = None,
-                deterministic_backward: Optional[bool] = None, grad_record: Optional[bool] = None):
-        """`exact_compositing=` / `deterministic_backward=` / `grad_record=` (keyword-only, beyond the reference): the three switches that affect
+                deterministic_backward: Optional[bool] = None, grad_record: Optional[bool] = None,
+                colour_gradients_only: Optional[bool] = None):
+        """`colour_gradients_only=True` (keyword-only, beyond the reference; with `colors_precomp`): the frame's backward pass computes the
+        gradient of `colors_precomp` ALONE -- one walk that sums the forward pass's blend weights, no geometry gradients, no per-Gaussian pass;
+        every other input's gradient is None (its `.grad` is left as it was).  For steps whose geometry is frozen and whose appearance alone is
+        optimised (WildGaussians.optimize_embedding, method.py:1755-1830).  None = the calling thread's default
+        (`with colour_gradients_only(True): ...`).  Refused with `shs`, `sh_mul` / `sh_offset` / clamps, `colors_precomp2`, `filter_3D`,
+        `sh_second` and `deterministic_backward=1`.
+
+        `exact_compositing=` / `deterministic_backward=` / `grad_record=` (keyword-only, beyond the reference): the three switches that affect
         results, PER CALL (wg_call_options, include/wg_rasterizer.h); None = the calling thread's default (`_C.call_options(...)` sets it for a
         `with` block -- for callers that cannot pass keywords); the frame's backward pass runs with its forward call's values.
 
@@ -254,4 +276,5 @@ class GaussianRasterizer(nn.Module):
             self.raster_settings, sh_mul, sh_offset, sh_pre_clamp_max, sh_post_clamp_max, binning_capacity, colors_precomp2, filter_3D,
             sh_second, sh_mul2, sh_offset2, sh_pre_clamp_max2, sh_post_clamp_max2,
             None if exact_compositing is None and deterministic_backward is None and grad_record is None else
-            dict(exact_compositing=exact_compositing, deterministic_backward=deterministic_backward, grad_record=grad_record))
+            dict(exact_compositing=exact_compositing, deterministic_backward=deterministic_backward, grad_record=grad_record),
+            colour_gradients_only=colour_gradients_only)

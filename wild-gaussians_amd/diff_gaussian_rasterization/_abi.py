@@ -44,4 +44,4 @@ class _BackwardArgs(C.Structure):  # wg_backward_args
                                     "campos", "subpixel_offset", "radii", "geom_buffer", "binning_buffer", "image_buffer", "dL_dpix", "dL_dmean2D",
                                     "dL_dconic", "dL_dopacity", "dL_dcolor", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot", "stream")] +
                 [("tone", C.POINTER(_ShTone)), ("tone2", C.POINTER(_ShTone)), ("sh_second", _i), ("second", C.POINTER(_SecondImage)),
-                 ("raw", C.POINTER(_RawGaussians)), ("options", C.POINTER(_CallOptions))])
+                 ("raw", C.POINTER(_RawGaussians)), ("options", C.POINTER(_CallOptions)), ("colour_gradients_only", _i)])

@@ -35,6 +35,11 @@ needs the few-line edits INTEGRATION.md lists.  What IS swapped, each with the r
   edited_module         (off by default) `GaussianModel._render_internal` -> the one of a module the INTEGRATOR supplies: a copy of the caller with
                         INTEGRATION.md section 5's "two_colour" or "two_tone" edit applied (the documented diff is the deliverable; this package
                         does not rewrite anybody's source -- tests/real_caller/render_edits.py is the test tool that builds such a module in memory)
+  embedding_optim       (OFF by default: the geometry parameters' `.grad` stay None instead of being filled and then zeroed)
+                        `WildGaussians.optimize_embedding` (method.py:1755-1830: 128 render-and-backward steps per test image whose only
+                        parameter is the appearance embedding, reached through `colors_precomp`) runs inside
+                        `diff_gaussian_rasterization.colour_gradients_only(True)`: every backward pass is the colour-only one
+                        Not with `edited_module` (ValueError): its render passes a second colour set or SH colours, which that pass refuses
   geometry_reuse        library option "geometry_reuse" = 1 (opt-in since round 4): the toned and depth calls of `_render_internal`
                         (method.py:1573-1631) ride on the raw call's projection and binning.  The caller's training loop qualifies
                         (it writes geometry only between a backward pass and the next forward pass); undo() switches it off again
@@ -46,7 +51,7 @@ import torch
 
 def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True, densification_stats: bool = True, activations: bool = True,
                  eval_sh: bool = True, geometry_reuse: bool = True, edited_module=None, filter_3d: bool = False, densify: bool = False,
-                 uncertainty_metrics: bool = False):
+                 embedding_optim: bool = False, uncertainty_metrics: bool = False):
     """-> a function that restores everything that was replaced.  `model`: an already constructed GaussianModel (e.g.
     `WildGaussians(...).model`) whose existing optimizer should be adopted too.
     edited_module (default None): a module object holding a copy of the caller with INTEGRATION.md section 5's edit of `_render_internal`
@@ -176,6 +181,19 @@ def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True
             return wg_fused_ssim.ssim_down(x, y, max_size=max_size)
         swap(method_module, "msssim", fused_msssim)
         swap(method_module, "ssim_down", fused_ssim_down)
+
+    if embedding_optim:
+        if edited_module is not None:   # its _render_internal passes colors_precomp2= / shs= + sh_second=, which the colour-only pass refuses
+            raise ValueError("embedding_optim cannot be combined with edited_module: the edited _render_internal makes calls the colour-only "
+                             "backward pass refuses (a second colour set, SH colours with tones)")
+        WG = method_module.WildGaussians
+        orig_optimize_embedding = WG.optimize_embedding
+
+        def optimize_embedding(self, *args, **kwargs):
+            from diff_gaussian_rasterization import colour_gradients_only
+            with colour_gradients_only(True):
+                return orig_optimize_embedding(self, *args, **kwargs)
+        swap(WG, "optimize_embedding", optimize_embedding)
 
     if edited_module is not None:
         edited = edited_module
