@@ -46,10 +46,13 @@ SOURCES = {
                                        # (include/wg_densify_prune.h), which switches contraction off for itself with a pragma
     "sh_eval.hip": [],                 # fused eval_sh fwd/bwd (include/wg_sh_eval.h)
     "adam.hip": ["-ffp-contract=off"],   # fused Adam step (include/wg_adam.h); no FMA contraction: torch's update, op for op
+    "appearance/mlp.hip": [],          # fused appearance MLP fwd/bwd on float32 MFMA (include/wg_appearance_mlp.h); in a subdirectory: the
+                                       # top level of csrc/ is the list of files bench.py's byte model names
 }
 HEADERS = ["wg_common.h", "wg_alpha.h", "wg_sort.h", "wg_act.h", os.path.join(INCLUDE, "wg_rasterizer.h"), os.path.join(INCLUDE, "wg_knn.h"),
            os.path.join(INCLUDE, "wg_ssim.h"), os.path.join(INCLUDE, "wg_activations.h"), os.path.join(INCLUDE, "wg_densify.h"), os.path.join(INCLUDE, "wg_adam.h"), os.path.join(INCLUDE, "wg_sh_eval.h"),
-           os.path.join(INCLUDE, "wg_filter3d.h"), os.path.join(INCLUDE, "wg_densify_prune.h"), os.path.join(INCLUDE, "wg_msssim.h")]
+           os.path.join(INCLUDE, "wg_filter3d.h"), os.path.join(INCLUDE, "wg_densify_prune.h"), os.path.join(INCLUDE, "wg_msssim.h"),
+           os.path.join(INCLUDE, "wg_appearance_mlp.h")]
 
 
 def _newer(target: str, deps) -> bool:
@@ -68,6 +71,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJ, src.replace(".hip", ".o"))
         objs.append(o)
+        os.makedirs(os.path.dirname(o), exist_ok=True)
         if force or _newer(o, [s] + hdrs):
             jobs.append([HIPCC] + COMMON + extra + EXTRA + FILE_EXTRA.get(src, []) + ["-c", s, "-o", o])
 

@@ -34,6 +34,13 @@ exact quantile that has no 2^24-element limit (include/wg_densify_prune.h):
     from wg_fused_gaussians import densify_and_prune, reset_opacity, quantile
     res = densify_and_prune(tensors, adam_state, stats, max_grad=..., min_opacity=..., extent=..., percent_dense=...,
                             enable_size_pruning=..., use_abs_gradient=...)   # res.tensors, res.adam_state, res.stats, res.counts, res.Q, res.origin
+
+The appearance MLP of EmbeddingModel.forward (method.py:874-900) as one float32-MFMA kernel forward and one backward that recomputes the hidden
+activations and saves only its inputs (include/wg_appearance_mlp.h); no `cat`, the image's embedding as a shared [E] vector or per row:
+
+    from wg_fused_gaussians import appearance_mlp, embedding_forward
+    offset_mul = appearance_mlp((features[..., :3], gembedding), list(model.mlp.parameters()), shared=aembedding)   # [P, 6]
+    toned = embedding_forward(model, gembedding, aembedding, features)                                              # EmbeddingModel.forward
 """
 from __future__ import annotations
 
@@ -538,3 +545,186 @@ def reset_opacity(opacities, scales, filter_3D, exp_avg=None, exp_avg_sq=None):
                                              None if exp_avg_sq is None else exp_avg_sq.data_ptr(),
                                              torch.cuda.current_stream(o.device).cuda_stream), "wg_reset_opacity")
     return out
+
+
+# ---- fused appearance MLP (include/wg_appearance_mlp.h, csrc/appearance/mlp.hip) ------------------------------------------------------
+class _MlpSegment(C.Structure):   # wg_appearance_mlp_segment
+    _fields_ = [("ptr", _vp), ("width", C.c_int32), ("reserved", C.c_int32), ("row_stride", C.c_int64)]
+
+
+class _MlpArgs(C.Structure):   # wg_appearance_mlp_args
+    _fields_ = [("struct_size", C.c_size_t), ("P", C.c_int64), ("num_segments", C.c_int32), ("shared_width", C.c_int32),
+                ("segments", _MlpSegment * 3), ("shared", _vp),
+                ("W1", _vp), ("b1", _vp), ("W2", _vp), ("b2", _vp), ("W3", _vp), ("b3", _vp),
+                ("out_scale", C.c_float), ("max_workgroups", C.c_int32), ("out", _vp), ("dL_dout", _vp),
+                ("grad_segment", _vp * 3), ("grad_row_stride", C.c_int64 * 3), ("grad_shared", _vp),
+                ("dW1", _vp), ("db1", _vp), ("dW2", _vp), ("db2", _vp), ("dW3", _vp), ("db3", _vp),
+                ("scratch", _vp), ("scratch_floats", C.c_int64), ("stream", _vp)]
+
+
+_lib.wg_appearance_mlp_scratch_floats.restype = C.c_int64
+_lib.wg_appearance_mlp_scratch_floats.argtypes = [C.c_int64, C.c_int32]
+_lib.wg_appearance_mlp_forward.restype = _i
+_lib.wg_appearance_mlp_forward.argtypes = [C.POINTER(_MlpArgs)]
+_lib.wg_appearance_mlp_backward.restype = _i
+_lib.wg_appearance_mlp_backward.argtypes = [C.POINTER(_MlpArgs)]
+MLP_HIDDEN, MLP_OUT, MLP_MAX_WIDTH, MLP_TILE_ROWS = 128, 6, 64, 64
+MLP_PARTIAL_FLOATS, MLP_SCRATCH_HEAD_FLOATS = 128 * 64 + 128 * 128 + 6 * 128 + 128 + 128 + 8, 128
+
+
+def appearance_mlp_scratch_floats(P, max_workgroups=0):
+    """Floats of scratch a backward call needs (max_workgroups = 0 asks the current device for its compute-unit count)."""
+    return _native._check(_lib.wg_appearance_mlp_scratch_floats(int(P), int(max_workgroups)), "wg_appearance_mlp_scratch_floats")
+
+
+def _mlp_row_view(t, name):
+    """A [P, w] float32 device tensor the kernel can read in place: unit stride along the row, any row stride >= w."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] >= 1):
+        raise RuntimeError(f"wg_fused_gaussians.appearance_mlp: {name} must be a [P, w] float32 tensor on a HIP device (there is no CPU path)")
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t
+
+
+def _mlp_fill(args, inputs, shared, weights, out_scale, max_workgroups, stream):
+    args.struct_size = C.sizeof(_MlpArgs)
+    args.P = inputs[0].shape[0]
+    args.num_segments = len(inputs)
+    for i, t in enumerate(inputs):
+        args.segments[i].ptr = t.data_ptr()
+        args.segments[i].width = t.shape[1]
+        args.segments[i].row_stride = t.stride(0) if t.shape[0] > 1 else t.shape[1]
+    args.shared_width = 0 if shared is None else shared.numel()
+    args.shared = None if shared is None else shared.data_ptr()
+    args.W1, args.b1, args.W2, args.b2, args.W3, args.b3 = [w.data_ptr() for w in weights]
+    args.out_scale = out_scale
+    args.max_workgroups = max_workgroups
+    args.stream = stream
+
+
+class _AppearanceMlp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, n_inputs, out_scale, max_workgroups, *tensors):
+        inputs = [_mlp_row_view(t, f"inputs[{i}]") for i, t in enumerate(tensors[:n_inputs])]
+        shared = tensors[n_inputs]
+        weights = tensors[n_inputs + 1:]
+        P = inputs[0].shape[0]
+        dev = inputs[0].device
+        Kr = sum(t.shape[1] for t in inputs)
+        if any(t.shape[0] != P or t.device != dev for t in inputs):
+            raise RuntimeError("wg_fused_gaussians.appearance_mlp: inputs must have the same number of rows, on one device")
+        if shared is not None:
+            if not (shared.is_cuda and shared.dtype == torch.float32 and shared.dim() == 1 and shared.device == dev):
+                raise RuntimeError("wg_fused_gaussians.appearance_mlp: shared must be a 1-D float32 tensor on the inputs' device")
+            shared = shared.contiguous()
+        K = Kr + (0 if shared is None else shared.numel())
+        shapes = [(MLP_HIDDEN, K), (MLP_HIDDEN,), (MLP_HIDDEN, MLP_HIDDEN), (MLP_HIDDEN,), (MLP_OUT, MLP_HIDDEN), (MLP_OUT,)]
+        if len(weights) != 6 or any(not (w.is_cuda and w.dtype == torch.float32 and tuple(w.shape) == s and w.device == dev)
+                                    for w, s in zip(weights, shapes)):
+            raise RuntimeError(f"wg_fused_gaussians.appearance_mlp: weights must be float32 (W1 b1 W2 b2 W3 b3) of shapes {shapes} on the "
+                               "inputs' device")
+        weights = [w.contiguous() for w in weights]
+        out = torch.empty((P, MLP_OUT), dtype=torch.float32, device=dev)
+        args = _MlpArgs()
+        _mlp_fill(args, inputs, shared, weights, out_scale, max_workgroups, torch.cuda.current_stream(dev).cuda_stream)
+        args.out = out.data_ptr()
+        with torch.cuda.device(dev):
+            _native._check(_lib.wg_appearance_mlp_forward(C.byref(args)), "wg_appearance_mlp_forward")
+        ctx.save_for_backward(*inputs, *([] if shared is None else [shared]), *weights)   # the inputs and nothing else
+        ctx.n_inputs, ctx.has_shared, ctx.out_scale, ctx.max_workgroups = n_inputs, shared is not None, out_scale, max_workgroups
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        saved = ctx.saved_tensors
+        n = ctx.n_inputs
+        inputs = list(saved[:n])
+        shared = saved[n] if ctx.has_shared else None
+        weights = list(saved[n + (1 if ctx.has_shared else 0):])
+        need = ctx.needs_input_grad[3:]
+        need_in, need_sh, need_w = need[:n], need[n], any(need[n + 1:])
+        P, dev = inputs[0].shape[0], inputs[0].device
+        g_out = g_out.contiguous()
+        args = _MlpArgs()
+        _mlp_fill(args, inputs, shared, weights, ctx.out_scale, ctx.max_workgroups, torch.cuda.current_stream(dev).cuda_stream)
+        args.dL_dout = g_out.data_ptr()
+        g_in = [torch.empty((P, t.shape[1]), dtype=torch.float32, device=dev) if nd else None for t, nd in zip(inputs, need_in)]
+        for i, g in enumerate(g_in):
+            if g is not None:
+                args.grad_segment[i] = g.data_ptr()
+                args.grad_row_stride[i] = g.shape[1]
+        g_sh = torch.empty_like(shared) if (shared is not None and need_sh) else None
+        if g_sh is not None:
+            args.grad_shared = g_sh.data_ptr()
+        g_w = [torch.empty_like(w) for w in weights] if need_w else [None] * 6
+        if need_w:
+            args.dW1, args.db1, args.dW2, args.db2, args.dW3, args.db3 = [g.data_ptr() for g in g_w]
+        with torch.cuda.device(dev):
+            floats = appearance_mlp_scratch_floats(P, ctx.max_workgroups)
+            scratch = torch.empty(floats, dtype=torch.float32, device=dev)
+            args.scratch, args.scratch_floats = scratch.data_ptr(), floats
+            _native._check(_lib.wg_appearance_mlp_backward(C.byref(args)), "wg_appearance_mlp_backward")
+        g_w = [g if nd else None for g, nd in zip(g_w, need[n + 1:])]
+        return (None, None, None, *g_in, g_sh, *g_w)
+
+
+def appearance_mlp(inputs, weights, shared=None, out_scale=0.01, max_workgroups=0):
+    """-> [P, 6] = out_scale * (W3 . relu(W2 . relu(W1 . cat(inputs..., shared) + b1) + b2) + b3), one HIP kernel in float32 on the matrix
+    cores; nothing but the inputs is saved for the backward pass, which recomputes the hidden activations (include/wg_appearance_mlp.h).
+
+    inputs   one to three [P, w_i] float32 tensors, read in place (a view with unit stride along the row and any row stride, such as
+             `features[..., :3]`, is not copied); the widths sum to 1..64
+    weights  (W1 [128, K], b1, W2 [128, 128], b2, W3 [6, 128], b3) as nn.Linear holds them, K = sum of widths (+ len(shared))
+    shared   optional [E <= 64] vector that every row carries behind its own columns (the image's appearance embedding)
+    Gradients go to whichever of inputs / shared / weights require them.  Two calls on the same inputs give the same bits."""
+    inputs = list(inputs)
+    if not 1 <= len(inputs) <= 3:
+        raise RuntimeError("wg_fused_gaussians.appearance_mlp: one to three inputs")
+    return _AppearanceMlp.apply(len(inputs), float(out_scale), int(max_workgroups), *inputs, shared, *weights)
+
+
+_SH_C0 = 0.28209479177387814
+
+
+def _mlp_covered(module):
+    """The module's weights if its `mlp` is Linear(K, 128)-ReLU-Linear(128, 128)-ReLU-Linear(128, 6), else None."""
+    nn = torch.nn
+    mlp = getattr(module, "mlp", None)
+    if not isinstance(mlp, nn.Sequential) or len(mlp) != 5:
+        return None
+    l1, r1, l2, r2, l3 = mlp
+    if not (isinstance(l1, nn.Linear) and isinstance(l2, nn.Linear) and isinstance(l3, nn.Linear) and isinstance(r1, nn.ReLU)
+            and isinstance(r2, nn.ReLU)):
+        return None
+    if (l1.out_features, l2.in_features, l2.out_features, l3.in_features, l3.out_features) != (128, 128, 128, 128, 6):
+        return None
+    if l1.bias is None or l2.bias is None or l3.bias is None:
+        return None
+    return (l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias)
+
+
+def embedding_forward(module, gembedding, aembedding, color, viewdir=None, *, original_forward=None, max_workgroups=0):
+    """EmbeddingModel.forward (wildgaussians/method.py:890-900) around the fused operator: `color[..., :3]`, `gembedding` and `aembedding`
+    are read in place (no `cat`); an `aembedding` of shape [E] is the shared path, one of shape [P, E] the per-row path.  Calls the fused
+    operator does not cover -- CPU tensors, a dtype other than float32, appearance_model_sh = True, an `mlp` of another shape -- go to the
+    module's own forward (`original_forward`, default type(module).forward): the caller's code, not a fallback of this library."""
+    weights = _mlp_covered(module)
+    tensors = (gembedding, aembedding, color)
+    ok = (weights is not None and not getattr(getattr(module, "config", None), "appearance_model_sh", False)
+          and all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in tensors + tuple(weights))
+          and color.dim() == 2 and gembedding.dim() == 2 and aembedding.dim() in (1, 2) and color.shape[1] >= 3 and color.shape[1] % 3 == 0
+          and weights[0].shape[1] == 3 + gembedding.shape[1] + aembedding.shape[-1] and 3 + gembedding.shape[1] <= MLP_MAX_WIDTH
+          and aembedding.shape[-1] <= MLP_MAX_WIDTH
+          and (aembedding.dim() == 1 or 3 + gembedding.shape[1] + aembedding.shape[1] <= MLP_MAX_WIDTH))
+    if not ok:
+        fwd = original_forward if original_forward is not None else type(module).forward
+        return fwd(module, gembedding, aembedding, color, viewdir)
+    input_color = color
+    if aembedding.dim() == 1:
+        om = appearance_mlp((color[..., :3], gembedding), weights, shared=aembedding, out_scale=0.01, max_workgroups=max_workgroups)
+    else:
+        om = appearance_mlp((color[..., :3], gembedding, aembedding), weights, out_scale=0.01, max_workgroups=max_workgroups)
+    offset, mul = torch.split(om, [3, 3], dim=-1)
+    offset = torch.cat((offset / _SH_C0, torch.zeros_like(input_color[..., 3:])), dim=-1)
+    mul = mul.repeat(1, input_color.shape[-1] // 3)
+    return input_color * mul + offset

@@ -32,6 +32,13 @@ needs the few-line edits INTEGRATION.md lists.  What IS swapped, each with the r
                         `method.msssim` (method.py:171-187) and `method.ssim_down` (:126-135), which UncertaintyModel._compute_losses
                         looks up as module globals on every step -> wg_fused_ssim.msssim / ssim_down (forward only); calls they do not
                         cover (CPU tensors, a dtype other than float32, an input that requires grad) go to the original functions
+  appearance_mlp        (OFF by default: results move within float32 rounding)
+                        `EmbeddingModel.forward` (method.py:890-900) -> wg_fused_gaussians.embedding_forward: `cat`, the three Linear
+                        layers, both ReLUs and `* 0.01` as one float32 MFMA kernel forward and one backward that recomputes the hidden
+                        activations (nothing of size P x 128 is kept or written); the two toning statements stay torch.  An `aembedding`
+                        of shape [E] takes the shared path.  Calls it does not cover (CPU tensors, a dtype other than float32,
+                        appearance_model_sh = True, an `mlp` that is not Linear-ReLU-Linear-ReLU-Linear with 128 / 128 / 6) go to the
+                        original forward
   edited_module         (off by default) `GaussianModel._render_internal` -> the one of a module the INTEGRATOR supplies: a copy of the caller with
                         INTEGRATION.md section 5's "two_colour" or "two_tone" edit applied (the documented diff is the deliverable; this package
                         does not rewrite anybody's source -- tests/real_caller/render_edits.py is the test tool that builds such a module in memory)
@@ -51,7 +58,7 @@ import torch
 
 def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True, densification_stats: bool = True, activations: bool = True,
                  eval_sh: bool = True, geometry_reuse: bool = True, edited_module=None, filter_3d: bool = False, densify: bool = False,
-                 embedding_optim: bool = False, uncertainty_metrics: bool = False):
+                 embedding_optim: bool = False, appearance_mlp: bool = False, uncertainty_metrics: bool = False):
     """-> a function that restores everything that was replaced.  `model`: an already constructed GaussianModel (e.g.
     `WildGaussians(...).model`) whose existing optimizer should be adopted too.
     edited_module (default None): a module object holding a copy of the caller with INTEGRATION.md section 5's edit of `_render_internal`
@@ -181,6 +188,14 @@ def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True
             return wg_fused_ssim.ssim_down(x, y, max_size=max_size)
         swap(method_module, "msssim", fused_msssim)
         swap(method_module, "ssim_down", fused_ssim_down)
+
+    if appearance_mlp:
+        EM = method_module.EmbeddingModel
+        orig_embedding_forward = EM.forward
+
+        def embedding_forward(self, gembedding, aembedding, color, viewdir=None):
+            return FG.embedding_forward(self, gembedding, aembedding, color, viewdir, original_forward=orig_embedding_forward)
+        swap(EM, "forward", embedding_forward)
 
     if embedding_optim:
         if edited_module is not None:   # its _render_internal passes colors_precomp2= / shs= + sh_second=, which the colour-only pass refuses
