@@ -48,11 +48,12 @@ SOURCES = {
     "adam.hip": ["-ffp-contract=off"],   # fused Adam step (include/wg_adam.h); no FMA contraction: torch's update, op for op
     "appearance/mlp.hip": [],          # fused appearance MLP fwd/bwd on float32 MFMA (include/wg_appearance_mlp.h); in a subdirectory: the
                                        # top level of csrc/ is the list of files bench.py's byte model names
+    "appearance/colour.hip": [],       # fused toned-colour operator over mlp.hip's tile walk (include/wg_appearance_colour.h)
 }
 HEADERS = ["wg_common.h", "wg_alpha.h", "wg_sort.h", "wg_act.h", os.path.join(INCLUDE, "wg_rasterizer.h"), os.path.join(INCLUDE, "wg_knn.h"),
            os.path.join(INCLUDE, "wg_ssim.h"), os.path.join(INCLUDE, "wg_activations.h"), os.path.join(INCLUDE, "wg_densify.h"), os.path.join(INCLUDE, "wg_adam.h"), os.path.join(INCLUDE, "wg_sh_eval.h"),
            os.path.join(INCLUDE, "wg_filter3d.h"), os.path.join(INCLUDE, "wg_densify_prune.h"), os.path.join(INCLUDE, "wg_msssim.h"),
-           os.path.join(INCLUDE, "wg_appearance_mlp.h")]
+           os.path.join(INCLUDE, "wg_appearance_mlp.h"), os.path.join(INCLUDE, "wg_appearance_colour.h")]
 
 
 def _newer(target: str, deps) -> bool:

@@ -41,6 +41,14 @@ activations and saves only its inputs (include/wg_appearance_mlp.h); no `cat`, t
     from wg_fused_gaussians import appearance_mlp, embedding_forward
     offset_mul = appearance_mlp((features[..., :3], gembedding), list(model.mlp.parameters()), shared=aembedding)   # [P, 6]
     toned = embedding_forward(model, gembedding, aembedding, features)                                              # EmbeddingModel.forward
+
+The toned precomputed colours of one image (method.py:1555, :1557, :890-900, :1592-1598) from its [E] appearance embedding in one kernel, with the
+embedding's gradient alone coming back in one kernel and a finishing launch, over the visible rows only (include/wg_appearance_colour.h); and the
+loop of optimize_embedding (method.py:1786-1815) around it:
+
+    from wg_fused_gaussians import toned_colours, fit_appearance_embedding, RowList
+    colours = toned_colours(features, gembedding, embedding, xyz, campos, weights, deg, rows=RowList(radii > 0))      # [P, 3]
+    embedding, losses, mses = fit_appearance_embedding(rasterizer, xyz, opacities, scales, rotations, features, gembedding, weights, embedding0, gt_image)
 """
 from __future__ import annotations
 
@@ -728,3 +736,225 @@ def embedding_forward(module, gembedding, aembedding, color, viewdir=None, *, or
     offset = torch.cat((offset / _SH_C0, torch.zeros_like(input_color[..., 3:])), dim=-1)
     mul = mul.repeat(1, input_color.shape[-1] // 3)
     return input_color * mul + offset
+
+
+# ---- fused toned colours (include/wg_appearance_colour.h, csrc/appearance/colour.hip) --------------------------------------------------
+class _ColourArgs(C.Structure):   # wg_appearance_colour_args
+    _fields_ = [("struct_size", C.c_size_t), ("P", C.c_int64), ("M", C.c_int64), ("rows", _vp),
+                ("features", _vp), ("features_row_stride", C.c_int64), ("deg", C.c_int32), ("gembedding_width", C.c_int32),
+                ("gembedding", _vp), ("gembedding_row_stride", C.c_int64), ("shared", _vp), ("shared_width", C.c_int32),
+                ("max_workgroups", C.c_int32), ("xyz", _vp), ("xyz_row_stride", C.c_int64), ("campos", _vp),
+                ("W1", _vp), ("b1", _vp), ("W2", _vp), ("b2", _vp), ("W3", _vp), ("b3", _vp),
+                ("out_scale", C.c_float), ("pre_clamp_max", C.c_float), ("post_clamp_max", C.c_float), ("reserved", C.c_int32),
+                ("colours", _vp), ("dL_dcolours", _vp), ("grad_shared", _vp), ("scratch", _vp), ("scratch_floats", C.c_int64),
+                ("stream", _vp)]
+
+
+_lib.wg_appearance_colour_scratch_floats.restype = C.c_int64
+_lib.wg_appearance_colour_scratch_floats.argtypes = [C.c_int64, C.c_int32]
+_lib.wg_appearance_colour_forward.restype = _i
+_lib.wg_appearance_colour_forward.argtypes = [C.POINTER(_ColourArgs)]
+_lib.wg_appearance_colour_backward.restype = _i
+_lib.wg_appearance_colour_backward.argtypes = [C.POINTER(_ColourArgs)]
+COLOUR_COEFFS, COLOUR_TILE_ROWS, COLOUR_PARTIAL_FLOATS = 48, 64, 128
+
+
+def appearance_colour_scratch_floats(M, max_workgroups=0):
+    """Floats of scratch a backward call over M listed rows needs (max_workgroups = 0 asks the current device for its compute-unit count)."""
+    return _native._check(_lib.wg_appearance_colour_scratch_floats(int(M), int(max_workgroups)), "wg_appearance_colour_scratch_floats")
+
+
+class RowList:
+    """The rows `toned_colours` evaluates, converted once: `index` (int32 [M] on the device) and M as a host number.  Built from a [P] bool
+    mask (one `nonzero`, the only host synchronisation) or from an integer index tensor (none); pass the object itself to later calls."""
+    __slots__ = ("index", "M")
+
+    def __init__(self, rows):
+        if isinstance(rows, RowList):
+            self.index, self.M = rows.index, rows.M
+            return
+        if not (torch.is_tensor(rows) and rows.is_cuda and rows.dim() == 1):
+            raise RuntimeError("wg_fused_gaussians.toned_colours: rows must be a 1-D bool mask or integer index tensor on a HIP device")
+        if rows.dtype == torch.bool:
+            rows = rows.nonzero().reshape(-1)
+        elif rows.dtype not in (torch.int32, torch.int64):
+            raise RuntimeError("wg_fused_gaussians.toned_colours: rows must be a bool mask or an int32 / int64 index tensor")
+        self.index = rows.detach().to(torch.int32).contiguous()
+        self.M = self.index.numel()
+
+
+def _colour_row_view(t, width, name):
+    """A [P, >= width] float32 device tensor the kernel reads in place: unit stride along the row, any row stride >= width."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] >= width):
+        raise RuntimeError(f"wg_fused_gaussians.toned_colours: {name} must be a [P, >= {width}] float32 tensor on a HIP device (there is no CPU path)")
+    if t.shape[1] and (t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
+        t = t.contiguous()
+    return t
+
+
+def _colour_fill(args, features, gemb, embedding, xyz, campos, index, M, weights, deg, pre, post, out_scale, max_workgroups, stream):
+    stride = lambda t: t.stride(0) if t.shape[0] > 1 else t.shape[1]   # noqa: E731
+    args.struct_size = C.sizeof(_ColourArgs)
+    args.P, args.M = features.shape[0], M
+    args.rows = None if index is None else index.data_ptr()
+    args.features, args.features_row_stride, args.deg = features.data_ptr(), stride(features), deg
+    G = gemb.shape[1]
+    args.gembedding_width = G
+    args.gembedding, args.gembedding_row_stride = (gemb.data_ptr(), stride(gemb)) if G else (None, 0)
+    args.shared, args.shared_width = embedding.data_ptr(), embedding.numel()
+    args.max_workgroups = max_workgroups
+    args.xyz, args.xyz_row_stride, args.campos = xyz.data_ptr(), stride(xyz), campos.data_ptr()
+    args.W1, args.b1, args.W2, args.b2, args.W3, args.b3 = [w.data_ptr() for w in weights]
+    args.out_scale, args.pre_clamp_max, args.post_clamp_max = out_scale, pre, post
+    args.stream = stream
+
+
+class _TonedColours(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, embedding, features, gemb, xyz, campos, index, M, deg, pre, post, out_scale, max_workgroups, *weights):
+        P, dev = features.shape[0], features.device
+        colours = torch.empty((P, 3), dtype=torch.float32, device=dev) if index is None else torch.zeros((P, 3), dtype=torch.float32, device=dev)
+        args = _ColourArgs()
+        _colour_fill(args, features, gemb, embedding, xyz, campos, index, M, weights, deg, pre, post, out_scale, max_workgroups,
+                     torch.cuda.current_stream(dev).cuda_stream)
+        args.colours = colours.data_ptr()
+        with torch.cuda.device(dev):
+            _native._check(_lib.wg_appearance_colour_forward(C.byref(args)), "wg_appearance_colour_forward")
+        ctx.save_for_backward(embedding, features, gemb, xyz, campos, *([] if index is None else [index]), *weights)   # the inputs and nothing else
+        ctx.has_index, ctx.conf = index is not None, (M, deg, pre, post, out_scale, max_workgroups)
+        return colours
+
+    @staticmethod
+    def backward(ctx, g):
+        saved = ctx.saved_tensors
+        embedding, features, gemb, xyz, campos = saved[:5]
+        index = saved[5] if ctx.has_index else None
+        weights = saved[6 if ctx.has_index else 5:]
+        M, deg, pre, post, out_scale, max_workgroups = ctx.conf
+        dev = features.device
+        g = g.contiguous()
+        grad = torch.empty_like(embedding)
+        args = _ColourArgs()
+        _colour_fill(args, features, gemb, embedding, xyz, campos, index, M, weights, deg, pre, post, out_scale, max_workgroups,
+                     torch.cuda.current_stream(dev).cuda_stream)
+        args.dL_dcolours, args.grad_shared = g.data_ptr(), grad.data_ptr()
+        with torch.cuda.device(dev):
+            floats = appearance_colour_scratch_floats(M, max_workgroups)
+            scratch = torch.empty(max(floats, 1), dtype=torch.float32, device=dev)
+            args.scratch, args.scratch_floats = scratch.data_ptr(), floats
+            _native._check(_lib.wg_appearance_colour_backward(C.byref(args)), "wg_appearance_colour_backward")
+        return (grad,) + (None,) * (11 + len(weights))
+
+
+def toned_colours(features, gembedding, embedding, xyz, campos, weights, deg, *, rows=None, pre_clamp_max=1.0, post_clamp_max=1.0,
+                  out_scale=0.01, max_workgroups=0):
+    """-> [P, 3] precomputed colours of the reference's toned path (wildgaussians/method.py:1555, :1557, :890-900, :1592-1598) in ONE kernel:
+    `clamp_max`, EmbeddingModel.forward with the image's `embedding` [E] shared by all rows, both clamps, `eval_sh` at the normalised
+    `xyz - campos` and `clamp_min(. + 0.5, 0)` (include/wg_appearance_colour.h).  Differentiable with respect to `embedding` ONLY: its
+    gradient comes from one kernel and a finishing launch, without any weight gradient, input gradient or [P, 48] tensor.  Any other tensor
+    argument that requires a gradient raises.
+
+    features    [P, >= 48] float32, coefficient-major (`features.view(P, 16, 3)`), read in place through its row stride
+    gembedding  [P, G], 3 + G <= 64;  embedding [E <= 64];  xyz [P, >= 3];  campos [3] ON THE DEVICE (the call does not synchronise)
+    weights     (W1 [128, 3 + G + E], b1, W2 [128, 128], b2, W3 [6, 128], b3) as nn.Linear holds them
+    deg         the active SH degree, 0..3
+    rows        None (all rows), a [P] bool mask, an integer index tensor, or a `RowList` built from either -- a mask costs one `nonzero`,
+                so build the RowList once and pass it to every later call.  Rows not listed are 0 in the result and read nothing.
+    A clamp bound of float("inf") means no clamp.  Two calls with the same max_workgroups give the same bits."""
+    weights = list(weights)
+    names = ["features", "gembedding", "xyz", "campos"] + [f"weights[{i}]" for i in range(len(weights))]
+    for name, t in zip(names, [features, gembedding, xyz, campos] + weights):
+        if torch.is_tensor(t) and t.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"wg_fused_gaussians.toned_colours: only the embedding receives a gradient; {name} is a constant here: detach it")
+    deg = int(deg)
+    if not 0 <= deg <= 3:
+        raise NotImplementedError("wg_fused_gaussians.toned_colours: degrees 0..3 are implemented")
+    features = _colour_row_view(features, COLOUR_COEFFS, "features")
+    gembedding = _colour_row_view(gembedding, 0, "gembedding")
+    xyz = _colour_row_view(xyz, 3, "xyz")
+    P, dev, G = features.shape[0], features.device, gembedding.shape[1]
+    for name, t, n in (("embedding", embedding, None), ("campos", campos, 3)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 and t.device == dev and (n is None or t.numel() == n)):
+            raise RuntimeError(f"wg_fused_gaussians.toned_colours: {name} must be a 1-D float32 tensor on the features' device"
+                               + ("" if n is None else f" with {n} elements"))
+    E = embedding.numel()
+    if gembedding.shape[0] != P or xyz.shape[0] != P or gembedding.device != dev or xyz.device != dev:
+        raise RuntimeError("wg_fused_gaussians.toned_colours: features, gembedding and xyz must have the same number of rows, on one device")
+    if not (1 <= E <= MLP_MAX_WIDTH and 3 + G <= MLP_MAX_WIDTH):
+        raise RuntimeError("wg_fused_gaussians.toned_colours: 3 + G <= 64 and 1 <= E <= 64 are implemented")
+    shapes = [(MLP_HIDDEN, 3 + G + E), (MLP_HIDDEN,), (MLP_HIDDEN, MLP_HIDDEN), (MLP_HIDDEN,), (MLP_OUT, MLP_HIDDEN), (MLP_OUT,)]
+    if len(weights) != 6 or any(not (torch.is_tensor(w) and w.is_cuda and w.dtype == torch.float32 and tuple(w.shape) == s and w.device == dev)
+                                for w, s in zip(weights, shapes)):
+        raise RuntimeError(f"wg_fused_gaussians.toned_colours: weights must be float32 (W1 b1 W2 b2 W3 b3) of shapes {shapes} on the features' device")
+    index, M = None, P
+    if rows is not None:
+        rl = rows if isinstance(rows, RowList) else RowList(rows)
+        if rl.index.device != dev:
+            raise RuntimeError("wg_fused_gaussians.toned_colours: rows must be on the features' device")
+        index, M = rl.index, rl.M
+    return _TonedColours.apply(embedding.contiguous(), features.detach(), gembedding.detach(), xyz.detach(), campos.detach().contiguous(), index, M, deg,
+                               float(pre_clamp_max), float(post_clamp_max), float(out_scale), int(max_workgroups),
+                               *[w.detach().contiguous() for w in weights])
+
+
+class _ScaleGrad(torch.autograd.Function):   # the caller's scale_grads: the value unchanged, the cotangent multiplied
+    @staticmethod
+    def forward(ctx, image, scale):
+        ctx.save_for_backward(scale)
+        return image.view_as(image)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.saved_tensors[0], None
+
+
+def fit_appearance_embedding(rasterizer, means3D, opacities, scales, rotations, features, gembedding, weights, embedding0, gt_image, *,
+                             campos=None, deg=None, iters=128, lr=0.1, loss="dssim+l1", lambda_dssim=0.2, grad_scale=None,
+                             pre_clamp_max=1.0, post_clamp_max=1.0, max_workgroups=0):
+    """The loop of WildGaussians.optimize_embedding (wildgaussians/method.py:1786-1815) at tensor level: `iters` Adam steps on the one [E]
+    appearance embedding of a test image, geometry and camera frozen.  -> (embedding [E] on the device, losses [iters], mses [iters] on the
+    host).
+
+    Once: one forward call of `rasterizer` finds the Gaussians that reach the image (`radii > 0`) and their RowList.  Each step:
+    `toned_colours(rows=...)`, `rasterizer(colors_precomp=...)` inside `colour_gradients_only(True)`, the loss ("dssim+l1":
+    wg_fused_ssim.l1_ssim_loss with `lambda_dssim`; "mse"), `torch.optim.Adam(lr=lr)`.  `grad_scale` (the caller's scale_grads masks,
+    multiplied together; broadcastable to the image) multiplies the image's cotangent and leaves its value unchanged.  The per-step losses
+    stay on the device; the host reads them once, at the end.  `campos` / `deg` default to the rasterizer's settings."""
+    from diff_gaussian_rasterization import colour_gradients_only
+    from wg_fused_ssim import l1_ssim_loss
+    if loss not in ("dssim+l1", "mse"):
+        raise ValueError(f"Unknown appearance optimization type {loss}")
+    rs = rasterizer.raster_settings
+    campos = rs.campos if campos is None else campos
+    deg = int(rs.sh_degree if deg is None else deg)
+    consts = [t.detach() for t in (means3D, opacities, scales, rotations, features, gembedding, campos, gt_image)]
+    means3D, opacities, scales, rotations, features, gembedding, campos, gt_image = consts
+    weights = [w.detach() for w in weights]
+    campos = campos.to(device=means3D.device, dtype=torch.float32).reshape(3)
+    means2D = torch.zeros_like(means3D)
+    with torch.no_grad():
+        radii = rasterizer(means3D=means3D, means2D=means2D, opacities=opacities, colors_precomp=torch.zeros_like(means3D), scales=scales,
+                           rotations=rotations)[1]
+    rows = RowList(radii > 0)
+    param = torch.nn.Parameter(embedding0.detach().clone().float())
+    optimizer = torch.optim.Adam([param], lr=lr)
+    iters = int(iters)
+    record = torch.zeros((2, max(iters, 1)), dtype=torch.float32, device=means3D.device)
+    with torch.enable_grad(), colour_gradients_only(True):
+        for i in range(iters):
+            optimizer.zero_grad()
+            colours = toned_colours(features, gembedding, param, means3D, campos, weights, deg, rows=rows, pre_clamp_max=pre_clamp_max,
+                                    post_clamp_max=post_clamp_max, max_workgroups=max_workgroups)
+            image = rasterizer(means3D=means3D, means2D=means2D, opacities=opacities, colors_precomp=colours, scales=scales, rotations=rotations)[0]
+            if grad_scale is not None:
+                image = _ScaleGrad.apply(image, grad_scale)
+            if loss == "mse":
+                value = mse = torch.nn.functional.mse_loss(image, gt_image)
+            else:
+                mse = torch.nn.functional.mse_loss(image.detach(), gt_image)
+                value = l1_ssim_loss(image, image, gt_image, lambda_dssim)
+            value.backward()
+            optimizer.step()
+            record[0, i], record[1, i] = value.detach(), mse.detach()
+    host = record[:, :iters].cpu()   # the loop's one host read
+    return param.detach(), host[0], host[1]
