@@ -32,6 +32,15 @@ needs the few-line edits INTEGRATION.md lists.  What IS swapped, each with the r
                         `method.msssim` (method.py:171-187) and `method.ssim_down` (:126-135), which UncertaintyModel._compute_losses
                         looks up as module globals on every step -> wg_fused_ssim.msssim / ssim_down (forward only); calls they do not
                         cover (CPU tensors, a dtype other than float32, an input that requires grad) go to the original functions
+  uncertainty_loss      (OFF by default: results move within float32 rounding, logged metrics move with them, and the dropout mask is drawn
+                        by another call than the reference's, so the random stream may differ)
+                        `UncertaintyModel._compute_losses` (method.py:363-433) -> wg_fused_uncertainty.compute_losses: everything around the
+                        frozen backbone (the three normalise / pad / resize chains, dropout2d + batch norm + the 1x1 convolution + softplus,
+                        the full-resolution maps and their six reductions, the cosine similarity, the DINO loss, the backward pass into
+                        conv_seg and bn) in HIP kernels, the metrics read with ONE device-to-host copy.  The backbone is still called
+                        through the model's own `_get_dino_cached`.  Calls it does not cover (another uncertainty_mode,
+                        uncertainty_dino_max_size set, CPU tensors, a batch, a prediction that requires grad, an initialised process
+                        group, a head of another form) go to the original method
   appearance_mlp        (OFF by default: results move within float32 rounding)
                         `EmbeddingModel.forward` (method.py:890-900) -> wg_fused_gaussians.embedding_forward: `cat`, the three Linear
                         layers, both ReLUs and `* 0.01` as one float32 MFMA kernel forward and one backward that recomputes the hidden
@@ -58,7 +67,8 @@ import torch
 
 def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True, densification_stats: bool = True, activations: bool = True,
                  eval_sh: bool = True, geometry_reuse: bool = True, edited_module=None, filter_3d: bool = False, densify: bool = False,
-                 embedding_optim: bool = False, appearance_mlp: bool = False, uncertainty_metrics: bool = False):
+                 embedding_optim: bool = False, uncertainty_loss: bool = False, appearance_mlp: bool = False,
+                 uncertainty_metrics: bool = False):
     """-> a function that restores everything that was replaced.  `model`: an already constructed GaussianModel (e.g.
     `WildGaussians(...).model`) whose existing optimizer should be adopted too.
     edited_module (default None): a module object holding a copy of the caller with INTEGRATION.md section 5's edit of `_render_internal`
@@ -188,6 +198,15 @@ def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True
             return wg_fused_ssim.ssim_down(x, y, max_size=max_size)
         swap(method_module, "msssim", fused_msssim)
         swap(method_module, "ssim_down", fused_ssim_down)
+
+    if uncertainty_loss:
+        import wg_fused_uncertainty
+        UM = method_module.UncertaintyModel
+        orig_compute_losses = UM._compute_losses
+
+        def _compute_losses(self, gt, prediction, prefix='', _cache_entry=None):
+            return wg_fused_uncertainty.compute_losses(self, gt, prediction, prefix, _cache_entry=_cache_entry, original=orig_compute_losses)
+        swap(UM, "_compute_losses", _compute_losses)
 
     if appearance_mlp:
         EM = method_module.EmbeddingModel
