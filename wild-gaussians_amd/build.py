@@ -51,12 +51,14 @@ SOURCES = {
     "appearance/colour.hip": [],       # fused toned-colour operator over mlp.hip's tile walk (include/wg_appearance_colour.h)
     "uncertainty/uncertainty.hip": [],   # fused uncertainty head and DINO loss around the backbone (include/wg_uncertainty.h); in a
                                          # subdirectory for the same reason as appearance/
+    "frames/frames.hip": [],           # device-resident training frames: uint8 store, fused unpack (include/wg_frames.h); no fast-math flag:
+                                       # its one division must stay correctly rounded
 }
 HEADERS = ["wg_common.h", "wg_alpha.h", "wg_sort.h", "wg_act.h", os.path.join(INCLUDE, "wg_rasterizer.h"), os.path.join(INCLUDE, "wg_knn.h"),
            os.path.join(INCLUDE, "wg_ssim.h"), os.path.join(INCLUDE, "wg_activations.h"), os.path.join(INCLUDE, "wg_densify.h"), os.path.join(INCLUDE, "wg_adam.h"), os.path.join(INCLUDE, "wg_sh_eval.h"),
            os.path.join(INCLUDE, "wg_filter3d.h"), os.path.join(INCLUDE, "wg_densify_prune.h"), os.path.join(INCLUDE, "wg_msssim.h"),
            os.path.join(INCLUDE, "wg_appearance_mlp.h"), os.path.join(INCLUDE, "wg_appearance_colour.h"),
-           os.path.join(INCLUDE, "wg_uncertainty.h")]
+           os.path.join(INCLUDE, "wg_uncertainty.h"), os.path.join(INCLUDE, "wg_frames.h")]
 
 
 def _newer(target: str, deps) -> bool:

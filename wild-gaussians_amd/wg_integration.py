@@ -59,6 +59,14 @@ needs the few-line edits INTEGRATION.md lists.  What IS swapped, each with the r
   geometry_reuse        library option "geometry_reuse" = 1 (opt-in since round 4): the toned and depth calls of `_render_internal`
                         (method.py:1573-1631) ride on the raw call's projection and binning.  The caller's training loop qualifies
                         (it writes geometry only between a backward pass and the next forward pass); undo() switches it off again
+
+A switch of its own, on a TRAINER object instead of the module, and off unless called (it changes device memory use):
+
+    undo = wg_integration.keep_training_frames_on_device(trainer)     # after WildGaussians.setup_train
+  frames on the device  `trainer.train_images`, `trainer.train_masks` (method.py:1716-1723, fetched at :1917-1918) -> wg_frame_store.FrameList:
+                        8-bit frames live on the device as uint8 and every access is one HIP kernel that writes the float32 tensor
+                        `.to(device)` would deliver, bit for bit; `uncertainty_model._images_cache` (method.py:262-264) ->
+                        wg_frame_store.FeatureCache, whose values stay on the device.  The caller's `.to(device)` lines become no-ops
 """
 from __future__ import annotations
 
@@ -249,4 +257,49 @@ def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True
             from diff_gaussian_rasterization import _C
             _C.set_option("geometry_reuse", reuse_before)
             _C.forget_geometry()
+    return undo
+
+
+def keep_training_frames_on_device(trainer, device=None, max_device_bytes=None, features: bool = True):
+    """Keep what `WildGaussians.train_iteration` fetches from the host on every step on the device instead (wg_frame_store): swaps
+    `trainer.train_images`, `trainer.train_masks` (when not None) and, with `features`, `trainer.model.uncertainty_model._images_cache` (when
+    there is such a model).  -> a function that puts the original lists back, untouched, and a plain dict holding CPU copies of every cached
+    feature entry (those added meanwhile included).  The function carries the stand-ins as `.images`, `.masks`, `.features` and their figures
+    as `.stats()`.  Off unless called.  device: default the current HIP device.  max_device_bytes: the budget all three share, in the order
+    images, masks, features; default half of the device memory that is free now.  What the budget does not admit, and tensors the store
+    does not cover, are served from the host as before."""
+    from wg_frame_store import Budget, FeatureCache, FrameList
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    budget = Budget(max_device_bytes, device)
+    saved = []
+
+    def swap(obj, name, new):
+        saved.append((obj, name, getattr(obj, name), new))
+        setattr(obj, name, new)
+        return new
+
+    images = swap(trainer, "train_images", FrameList(trainer.train_images, device, budget))
+    masks = None
+    if getattr(trainer, "train_masks", None) is not None:
+        masks = swap(trainer, "train_masks", FrameList(trainer.train_masks, device, budget))
+    cache, uncertainty_model = None, getattr(getattr(trainer, "model", None), "uncertainty_model", None)
+    if features and uncertainty_model is not None and isinstance(getattr(uncertainty_model, "_images_cache", None), dict):
+        cache = FeatureCache(device, budget, initial=uncertainty_model._images_cache)
+        uncertainty_model._images_cache = cache
+
+    def undo():
+        nonlocal cache
+        while saved:
+            obj, name, old, new = saved.pop()
+            new.release()
+            setattr(obj, name, old)
+        if cache is not None:
+            uncertainty_model._images_cache = cache.to_host_dict()
+            cache.clear()
+            cache = None
+
+    undo.images, undo.masks, undo.features = images, masks, cache
+    undo.stats = lambda: {"budget_bytes": budget.total, "used_bytes": budget.used, "images": images.stats(),
+                          "masks": masks.stats() if masks is not None else None,
+                          "features": undo.features.stats() if undo.features is not None else None}
     return undo
