@@ -53,8 +53,11 @@ typedef enum wg_status {
  * speculative forward re-issues a frame that did not fit its predicted buffer); the buffer returned last is the one in use. */
 typedef char* (*wg_alloc_fn)(size_t bytes, void* user);
 
-/* Scratch sizes (bytes), for callers that preallocate (the binning size is an upper bound). */
+/* Scratch sizes (bytes), for callers that preallocate (the binning size is an upper bound).  wg_geometry_buffer_size_rows: what a forward
+ * call with plain SH colours (no tone, no second set) and forward_only = 0 asks geometry_alloc for -- 40 bytes per Gaussian more, rounded up to
+ * 256, the frame's backward rows; every other forward call asks for wg_geometry_buffer_size. */
 size_t wg_geometry_buffer_size(int P);
+size_t wg_geometry_buffer_size_rows(int P);
 size_t wg_image_buffer_size(int width, int height);
 size_t wg_binning_buffer_size(int num_rendered);
 size_t wg_image_accumulation_offset(int width, int height); /* bytes from final_T to accumulation[H*W] */
@@ -149,7 +152,8 @@ typedef struct wg_recolor_parent {
 } wg_recolor_parent;
 
 typedef struct wg_forward_args {
-    size_t struct_size;   /* the CALLER's sizeof(wg_forward_args): fields are only ever appended; a shorter (older) struct is accepted
+    size_t struct_size;   /* the CALLER's sizeof(wg_forward_args): fields are only ever appended (one exception: forward_only, below, took
+                             what was padding); a shorter (older) struct is accepted
                              from version 0.5's 288 bytes on, its missing tail reads as absent; a longer (newer) one is refused */
     wg_alloc_fn geometry_alloc; void* geometry_user;
     wg_alloc_fn binning_alloc;  void* binning_user;
@@ -171,6 +175,13 @@ typedef struct wg_forward_args {
     int binning_capacity;              /* > 0: NO host rendezvous at all (hipGraph capture): the caller's capacity in instances; returns it
                                           (hand it to backward as R); a frame that does not fit gives a NaN image and zero gradients,
                                           wg_forward_status() tells afterwards.  <= 36864 tiles, no debug, no deterministic backward. */
+    int forward_only;                  /* 1: the caller expects NO backward call for this frame (grad mode off, nothing requires a gradient): a
+                                          frame with plain SH colours then skips the 40-byte backward row per Gaussian it would leave for the
+                                          per-Gaussian backward kernel, and asks geometry_alloc for wg_geometry_buffer_size(P) instead of
+                                          wg_geometry_buffer_size_rows(P).  A hint, not a contract: a backward call on such a frame is served by
+                                          the kernel that re-reads the SH block.  The field takes the four bytes that were padding between
+                                          binning_capacity and options since version 0.5, so the struct keeps its 288 bytes and its first
+                                          published layout: a caller built against an older header, whose structs are zero-initialised, says 0. */
     const wg_call_options* options;
 } wg_forward_args;
 
@@ -231,6 +242,11 @@ typedef struct wg_image_view {
     const uint32_t* order_bwd;  /* [tiles] launch order of the backward render kernel (written by the frame's backward call) */
 } wg_image_view;
 int wg_view_geometry(char* geom_buffer, int P, wg_geometry_view* out);
+/* The backward rows of a frame with plain SH colours rendered with forward_only = 0: [P*10] floats, per Gaussian nine direction terms
+ * T[ch][axis] = sum_k dB_k/d axis * sh[k][ch], then opacity*coef; zeros for a culled Gaussian.  buffer_bytes: the size of the frame's geometry
+ * buffer; *rows = NULL when it is too small to hold the array (a frame that left none: its buffer is wg_geometry_buffer_size(P)).  A call of
+ * its own, not a field of wg_geometry_view: that struct carries no size, so it cannot grow under callers built against an older header. */
+int wg_view_backward_rows(char* geom_buffer, int P, size_t buffer_bytes, const float** rows);
 int wg_view_binning(char* binning_buffer, int R, wg_binning_view* out);
 int wg_view_image(char* image_buffer, int width, int height, wg_image_view* out);
 

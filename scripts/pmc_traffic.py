@@ -29,19 +29,39 @@ STAGE_OF = {"preprocess_kernel": "preprocess", "tile_count_kernel": "scan", "chu
             "tile_front_sort_kernel": "sort", "render_fixup_kernel": "render_fixup", "tile_order_kernel": "tile_ranges",
             "split_hist_kernel": "scan", "split_pick_kernel": "scan", "tile_scatter_far_kernel": "duplicate_keys", "render_forward_kernel": "render_forward",
             "render_backward_kernel": "render_backward", "preprocess_backward_kernel": "preprocess_backward"}
-vals = {}
+# A stage's kernels are summed, but of one kernel only ONE instantiation belongs to a step: bench.py --full also runs forward-only passes,
+# whose per-Gaussian kernel is another instantiation (no backward row: preprocess_kernel's last template argument, ROW, false) than the
+# training step's.  A summary that holds a backward kernel is a training workload's: its step runs the ROW instantiation.  Where that rule
+# does not decide (another kernel, a forward-only workload) the instantiation with the most dispatches is taken, and two of one kernel with the
+# same count are an error rather than a guess.  The others are listed under `other_instantiations` and not added in.
+per_inst = {}
 for line in open(sys.argv[1]):
     m = re.match(r"(\S.*?)\s+(FETCH_SIZE|WRITE_SIZE|SQ_INSTS_VALU|SQ_INSTS_SALU|SQ_INSTS_LDS|SQ_ACTIVE_INST_VALU|GRBM_GUI_ACTIVE|SQ_LDS_BANK_CONFLICT|"
                  r"SQ_INSTS_VALU_TRANS_F32|SQ_THREAD_CYCLES_VALU|SQ_INSTS_VALU_ADD_F32|SQ_INSTS_VALU_MUL_F32|SQ_INSTS_VALU_FMA_F32|SQ_INST_CYCLES_VALU|"
-                 r"SQ_INSTS_VALU_INT32)\s+dispatches=\s*\d+\s+per_dispatch=\s*(\d+)", line)
+                 r"SQ_INSTS_VALU_INT32)\s+dispatches=\s*(\d+)\s+per_dispatch=\s*(\d+)", line)
     if not m:
         continue
-    name = re.sub(r"^void ", "", m.group(1)).split("(")[0].replace("wg::", "").split("<")[0]
-    st = STAGE_OF.get(name)
-    if st:
+    inst = re.sub(r"^void ", "", m.group(1)).split("(")[0].replace("wg::", "")
+    name = inst.split("<")[0]
+    if name in STAGE_OF:
         key = m.group(2) + "_KiB" if m.group(2).endswith("_SIZE") else m.group(2)  # SQ_INSTS_*: wave-instructions per launch
-        d = vals.setdefault(st, {"FETCH_SIZE_KiB": 0, "WRITE_SIZE_KiB": 0})
-        d[key] = d.get(key, 0) + int(m.group(3))
+        e = per_inst.setdefault(name, {}).setdefault(inst, {"dispatches": 0, "counters": {}})
+        e["dispatches"] = max(e["dispatches"], int(m.group(3)))
+        e["counters"][key] = int(m.group(4))
+vals, others = {}, {}
+for name, insts in per_inst.items():
+    ranked = sorted(insts.items(), key=lambda kv: -kv[1]["dispatches"])
+    if name == "preprocess_kernel" and "preprocess_backward_kernel" in per_inst:
+        row = [kv for kv in ranked if re.search(r",\s*true\s*>$", kv[0]) and kv[0].count(",") == 4]
+        if row:
+            ranked = row[:1] + [kv for kv in ranked if kv is not row[0]]
+    elif len(ranked) > 1 and ranked[0][1]["dispatches"] == ranked[1][1]["dispatches"]:
+        raise SystemExit(f"{name}: {ranked[0][0]} and {ranked[1][0]} ran equally often; which belongs to the step?")
+    d = vals.setdefault(STAGE_OF[name], {"FETCH_SIZE_KiB": 0, "WRITE_SIZE_KiB": 0})
+    for key, v in ranked[0][1]["counters"].items():
+        d[key] = d.get(key, 0) + v
+    for inst, e in ranked[1:]:
+        others[inst] = dict(e["counters"], dispatches=e["dispatches"], counted_instead=ranked[0][0])
 try:
     import bench
     st = bench.profile_stamps()   # kernel sources + the device code of the library as built (bench.device_code_sha)
@@ -66,6 +86,8 @@ for st in out["stages"].values():
         st["valu_wave_cycles_per_simd_cycle"] = round(4.0 * st["SQ_ACTIVE_INST_VALU"] / (1024.0 * st["GRBM_GUI_ACTIVE"] / 8.0), 3)
     if st.get("SQ_ACTIVE_INST_VALU") and st.get("SQ_THREAD_CYCLES_VALU"):
         st["thread_utilisation"] = round(st["SQ_THREAD_CYCLES_VALU"] / (64.0 * st["SQ_ACTIVE_INST_VALU"]), 4)
+if others:
+    out["other_instantiations"] = others
 out["valu_note"] = ("thread_utilisation = SQ_THREAD_CYCLES_VALU / (64 * SQ_ACTIVE_INST_VALU): mean active lanes per executed vector instruction; "
                     "valu_wave_cycles_per_simd_cycle = 4 * SQ_ACTIVE_INST_VALU / (1024 SIMDs * GRBM_GUI_ACTIVE / 8 XCDs): summed over waves, may exceed 1")
 print(json.dumps(out, indent=1))

@@ -451,6 +451,11 @@ size_t wg_geometry_buffer_size(int P) {
     const bool lists = p >= (size_t)options_snapshot().band_list_min_p;
     return required_bytes([&](char*& c) { wg::GeometryState::fromChunk(c, p, lists); });
 }
+size_t wg_geometry_buffer_size_rows(int P) {
+    const size_t p = (size_t)(P > 0 ? P : 0);
+    const bool lists = p >= (size_t)options_snapshot().band_list_min_p;
+    return required_bytes([&](char*& c) { wg::GeometryState::fromChunk(c, p, lists, true); });
+}
 size_t wg_image_buffer_size(int width, int height) {
     const size_t N = (size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0);
     const size_t tiles = (size_t)((width + wg::TILE_X - 1) / wg::TILE_X) * (size_t)((height + wg::TILE_Y - 1) / wg::TILE_Y);
@@ -644,19 +649,33 @@ void order_tables_release() {
     g_order_tables.clear();
 }
 
-struct FrameMode { const void* image; int exact; };
+// row / geom: whether the frame's forward call left backward rows (wg_common.h: BWD_ROW_FLOATS), and in which geometry buffer
+struct FrameMode { const void* image; int exact; int row; const void* geom; };
+// read-only counters of the process (wg_get_option): forward calls that left backward rows, backward calls that ran on them
+std::atomic<uint64_t> g_row_frames{0}, g_row_backwards{0};
 std::mutex g_mode_mu;
 FrameMode g_modes[64];
 unsigned g_mode_head = 0;
 const void* image_key(const char* image_buffer) {
     return reinterpret_cast<const void*>((reinterpret_cast<uintptr_t>(image_buffer) + wg::ALIGN - 1) & ~(uintptr_t)(wg::ALIGN - 1));
 }
-void remember_mode(const char* image_buffer, int exact) {
+void remember_mode(const char* image_buffer, int exact, int row, const char* geom_buffer) {
     const void* k = image_key(image_buffer);
+    const void* gk = image_key(geom_buffer);
     std::lock_guard<std::mutex> l(g_mode_mu);
     for (auto& m : g_modes)
-        if (m.image == k) { m.exact = exact; return; }
-    g_modes[g_mode_head++ % 64] = {k, exact};
+        if (m.image == k) { m.exact = exact; m.row = row; m.geom = gk; return; }
+    g_modes[g_mode_head++ % 64] = {k, exact, row, gk};
+}
+// whether the frame of this image buffer left backward rows in this geometry buffer (a frame that is not remembered did not, as far as its
+// backward call can tell: it takes the kernel that needs none)
+bool remembered_row(const char* image_buffer, const char* geom_buffer) {
+    const void* k = image_key(image_buffer);
+    const void* gk = image_key(geom_buffer);
+    std::lock_guard<std::mutex> l(g_mode_mu);
+    for (auto& m : g_modes)
+        if (m.image == k) return m.row != 0 && m.geom == gk;
+    return false;
 }
 // -1: not remembered (older than 64 frames: the caller is trusted)
 int remembered_mode(const char* image_buffer) {
@@ -693,7 +712,8 @@ int wg_rasterize_forward(wg_alloc_fn geometry_alloc, void* geometry_user, wg_all
     return forward_impl(a);
 }
 
-// struct_size: a caller built against an OLDER header hands over a shorter struct (fields are only ever appended): accepted from the
+// struct_size: a caller built against an OLDER header hands over a shorter struct (fields are only ever appended -- but for
+// wg_forward_args::forward_only, which took four bytes of padding inside the first layout: a hint whose absence, or whose garbage, changes no result): accepted from the
 // first published layout on, the missing tail reads as zero / NULL = absent.  A larger one (a newer header) is refused: its tail may ask
 // for something this library does not know.
 constexpr size_t FORWARD_ARGS_V05 = 288, BACKWARD_ARGS_V05 = 312;   // sizeof of the first published layouts (version 0.5, LP64)
@@ -795,6 +815,7 @@ struct ForwardFrame {
     uint32_t* order_table = nullptr;
     uint32_t order_slots = 0, near_per_tile = 0;
     bool try_split = false, lazy_colour = false;
+    bool row = false;   // the frame leaves backward rows: plain SH colours and a backward call expected (wg_forward_args::forward_only = 0)
     Mailbox* mbox = nullptr;
     // ---- what depends on the instance count, as functions of it (used by the speculative and by the classic flow alike) ----
     // Longest per-tile list decides the binning path: full register sort of every tile, lazy front sort when lists are long,
@@ -837,11 +858,11 @@ int ForwardFrame::preprocess_and_count(wg::FwdOrderArgs& fo) const {
             fo.table = nullptr;
         }
     }
-    WG_STAGE(WG_STAGE_PREPROCESS, wg::launch_preprocess(fp, device_tone(a.tone, a.tone2, a.sh_second != 0), geom, a.radii, lazy_colour, stream), "preprocess");
+    WG_STAGE(WG_STAGE_PREPROCESS, wg::launch_preprocess(fp, device_tone(a.tone, a.tone2, a.sh_second != 0), geom, a.radii, lazy_colour, row, stream), "preprocess");
     if (!huge_frame) {
         if (try_split)
             WG_STAGE(WG_STAGE_SCAN, wg::launch_split_threshold(P, geom, img, tiles, opt.near_split == 1, near_per_tile, stream), "split_threshold");
-        if (lazy_colour) WG_STAGE(WG_STAGE_PREPROCESS, wg::launch_sh_colour(fp, geom, img.split, false, stream), "sh_colour_near");
+        if (lazy_colour) WG_STAGE(WG_STAGE_PREPROCESS, wg::launch_sh_colour(fp, geom, img.split, false, row, stream), "sh_colour_near");
         const bool box = opt.box_count == 1 || (opt.box_count < 0 && (P >= opt.band_list_min_p || t_split.last_instances_per_tile >= 1500u));
         WG_STAGE(WG_STAGE_SCAN, wg::launch_tile_count(P, geom, img, gx, tiles, try_split, box, opt.fused_scan != 0, stream), "tile_count");
     } else {
@@ -926,7 +947,7 @@ int ForwardFrame::enqueue_tail(const wg::BinningState& bin, uint32_t R, uint32_t
                  wg::launch_render_fixup(code_bits, width, height, gx, gy, img, bin, geom, a.subpixel_offset, a.background, a.out_color, out_color2, opt.lazy, try_split, 0, opt.exact_compositing != 0, (wg::HostMailbox*)nullptr, guard, stream),
                  "render_fixup");
         if (far) {  // all return at once unless some tile ran out of near instances with pixels still accumulating
-            if (lazy_colour) WG_STAGE(WG_STAGE_PREPROCESS, wg::launch_sh_colour(fp, geom, img.split, true, stream), "sh_colour_far");
+            if (lazy_colour) WG_STAGE(WG_STAGE_PREPROCESS, wg::launch_sh_colour(fp, geom, img.split, true, row, stream), "sh_colour_far");
             WG_STAGE(WG_STAGE_DUPLICATE_KEYS, wg::launch_tile_scatter_far(P, geom, img, bin, gx, tiles, code_bits, guard, stream), "tile_scatter_far");
             WG_STAGE(WG_STAGE_RENDER_FIXUP,
                      wg::launch_render_fixup(code_bits, width, height, gx, gy, img, bin, geom, a.subpixel_offset, a.background, a.out_color, out_color2, opt.lazy, true, 1, opt.exact_compositing != 0, mbox ? mbox->dev : (wg::HostMailbox*)nullptr, guard, stream),
@@ -984,11 +1005,17 @@ static int forward_impl(const wg_forward_args& a) {
     const int P = f.P, tiles = f.tiles;
 
     const bool band_lists = (size_t)P >= (size_t)opt.band_list_min_p;  // size and carving from the same snapshot
-    char* geom_chunk = a.geometry_alloc(required_bytes([&](char*& c) { wg::GeometryState::fromChunk(c, (size_t)P, band_lists); }), a.geometry_user);
+    // Backward rows: every route that evaluates plain (untoned, single) SH colours leaves them, unless the caller expects no backward call;
+    // only such a frame's geometry buffer holds the array (wg_geometry_buffer_size_rows)
+    f.row = P > 0 && a.forward_only == 0 && a.shs != nullptr && a.colors_precomp == nullptr && a.tone == nullptr && a.tone2 == nullptr && !a.sh_second &&
+            a.second == nullptr;
+    const bool rows = f.row;
+    char* geom_chunk = a.geometry_alloc(required_bytes([&](char*& c) { wg::GeometryState::fromChunk(c, (size_t)P, band_lists, rows); }), a.geometry_user);
     char* img_chunk = a.image_alloc(wg_image_buffer_size(a.width, a.height), a.image_user);
     if (!geom_chunk || !img_chunk) return WG_ERR_ALLOC;
-    remember_mode(img_chunk, opt.exact_compositing ? 1 : 0);
-    f.geom = wg::GeometryState::fromChunk(geom_chunk, (size_t)P, band_lists);
+    remember_mode(img_chunk, opt.exact_compositing ? 1 : 0, f.row ? 1 : 0, geom_chunk);
+    if (f.row) g_row_frames.fetch_add(1, std::memory_order_relaxed);
+    f.geom = wg::GeometryState::fromChunk(geom_chunk, (size_t)P, band_lists, rows);
     f.img = wg::ImageState::fromChunk(img_chunk, (size_t)a.width * a.height, (size_t)tiles);
     f.fp = forward_params(a, opt, f.gx, f.gy);
     f.order_table = (P > 0 && !f.debug) ? order_table_for(opt, tiles, f.stream, &f.order_slots) : nullptr;
@@ -1226,6 +1253,14 @@ static int backward_impl(const wg_backward_args& a) {
     bp.P = P; bp.D = D; bp.M = M; bp.W = width; bp.H = height;
     bp.means3D = means3D; bp.shs = shs; bp.scales = scales; bp.scale_modifier = scale_modifier; bp.rotations = rotations;
     bp.cov3D = (cov3D_precomp != nullptr) ? cov3D_precomp : geom.cov3D;  // rasterizer_impl.cu:418
+    // The frame's forward call left backward rows and this call is the plain-SH backward they were made for: the per-Gaussian kernel reads
+    // the row instead of the SH block and the splat record, and recomputes the covariance it would otherwise read back.
+    if (shs != nullptr && tone == nullptr && tone2 == nullptr && !sh_second && second == nullptr && remembered_row(a.image_buffer, a.geom_buffer)) {
+        char* gb = a.geom_buffer;   // (the frame's buffer holds the row array: carved as its forward call carved it)
+        bp.bwd_row = wg::GeometryState::fromChunk(gb, (size_t)P, false, true).bwd_row;
+        g_row_backwards.fetch_add(1, std::memory_order_relaxed);
+        if (cov3D_precomp == nullptr && scales != nullptr) bp.cov3D = nullptr;
+    }
     bp.viewmatrix = viewmatrix; bp.projmatrix = projmatrix; bp.campos = campos;
     bp.tan_fovx = tan_fovx; bp.tan_fovy = tan_fovy;
     bp.focal_y = height / (2.0f * tan_fovy);
@@ -1307,6 +1342,13 @@ int wg_view_geometry(char* geom_buffer, int P, wg_geometry_view* out) {
     out->clamped = g.clamped;
     out->tiles_touched = g.tiles_touched;
     out->point_offsets = g.point_offsets;
+    return WG_OK;
+}
+
+int wg_view_backward_rows(char* geom_buffer, int P, size_t buffer_bytes, const float** rows) {
+    if (!geom_buffer || !rows || P < 0) return WG_ERR_INVALID_ARGUMENT;
+    const size_t need = required_bytes([&](char*& c) { wg::GeometryState::fromChunk(c, (size_t)P, false, true); });   // (band lists, if any, lie behind the rows)
+    *rows = buffer_bytes >= need ? wg::GeometryState::fromChunk(geom_buffer, (size_t)P, false, true).bwd_row : nullptr;
     return WG_OK;
 }
 
@@ -1423,6 +1465,9 @@ int wg_get_option(const char* name) {
     if (std::strcmp(name, "forward_polls_waited") == 0) return (int)std::min<uint64_t>(t_wait.waited, 0x7fffffffu);
     if (std::strcmp(name, "forward_wait_us_total") == 0) return (int)std::min(t_wait.wait_us, 2147483647.0);
     if (std::strcmp(name, "forward_wait_us_last") == 0) return (int)std::min(t_wait.last_wait_us, 2147483647.0);
+    // read-only counters of the process: forward calls that left backward rows / backward calls that took the row kernel
+    if (std::strcmp(name, "backward_row_frames") == 0) return (int)std::min<uint64_t>(g_row_frames.load(std::memory_order_relaxed), 0x7fffffffu);
+    if (std::strcmp(name, "backward_row_calls") == 0) return (int)std::min<uint64_t>(g_row_backwards.load(std::memory_order_relaxed), 0x7fffffffu);
     const OptionRow* r = find_option(name);
     return r ? r->get(options_snapshot()) : -1;
 }

@@ -41,7 +41,7 @@ size_t query_sort_temp_bytes(size_t R) {
 // hold FEWER than 65536 Gaussians (65536 of them on one tile would carry the near half into the total half), i.e. P <= 65535 * BIN_CHUNKS
 bool GeometryState::band_lists_possible(size_t P) { return (P + BIN_CHUNKS - 1) / BIN_CHUNKS <= 65535; }
 
-GeometryState GeometryState::fromChunk(char*& chunk, size_t P, bool lists) {
+GeometryState GeometryState::fromChunk(char*& chunk, size_t P, bool lists, bool rows) {
     GeometryState g;
     const size_t Pa = P ? P : 1;
     carve(chunk, g.depths, Pa);
@@ -56,6 +56,8 @@ GeometryState GeometryState::fromChunk(char*& chunk, size_t P, bool lists) {
                                                                                //  sum; a whole number of float4: the clear below writes float4)
     g.scan_temp_bytes = query_scan_temp_bytes(Pa);
     carve(chunk, g.scan_temp, g.scan_temp_bytes);
+    g.bwd_row = nullptr;
+    if (rows) carve(chunk, g.bwd_row, Pa * BWD_ROW_FLOATS);
     lists = lists && band_lists_possible(P);
     carve(chunk, g.band_list, lists ? (size_t)BIN_CHUNKS * 8 * ((Pa + BIN_CHUNKS - 1) / BIN_CHUNKS) : 0);
     carve(chunk, g.band_cnt, lists ? (size_t)BIN_CHUNKS * 16 : 0);   // per (chunk, band): the near (or, without a split, all) candidates, then the far ones

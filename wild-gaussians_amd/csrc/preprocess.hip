@@ -55,11 +55,16 @@ constexpr int SH_PITCH4 = 13;
 // are left zero, the clamp flags cleared and the SH block is not read; sh_colour_kernel below colours the Gaussians whose instances can be
 // walked at all: the NEAR ones before the binning chain, the far ones only when a tile asks for its far instances.  The 192-byte SH block is
 // four fifths of what this kernel reads per Gaussian, and at 10 M Gaussians / 4K nine Gaussians in ten are far.
-template <int SH_MODE, bool PRECOMP, bool TONE, bool GEOM_ONLY = false>   // SH_MODE: 0 generic layout, 1 coalesced block through LDS, 2 the same with non-temporal loads
+// ROW (plain SH colours of a frame that expects a backward call): the kernel also leaves the Gaussian's backward row (wg_common.h: bwd_row_terms)
+// -- with GEOM_ONLY zeros and the combined opacity; sh_colour_kernel fills in the direction terms of the Gaussians it colours.  The wave's 64 rows
+// go out through the LDS stage as one contiguous 2560-byte span.
+template <int SH_MODE, bool PRECOMP, bool TONE, bool GEOM_ONLY = false, bool ROW = false>   // SH_MODE: 0 generic layout, 1 coalesced block through LDS, 2 the same with non-temporal loads
 __global__ void __launch_bounds__(64) preprocess_kernel(FwdParams p, GeometryState g, int* __restrict__ radii_out, ToneArg<TONE> tone) {
     static_assert(!GEOM_ONLY || (SH_MODE == 0 && !TONE), "the geometry-only instantiation loads no SH block");
+    static_assert(!ROW || !TONE, "toned frames keep the backward kernel that re-reads the SH block");
     constexpr bool FAST_SH = SH_MODE != 0, NT = SH_MODE == 2;
-    __shared__ float4 stage[FAST_SH ? 64 * SH_PITCH4 : 1];
+    constexpr int ROW_STAGE4 = 64 * BWD_ROW_FLOATS / 4;
+    __shared__ float4 stage[FAST_SH ? 64 * SH_PITCH4 : (ROW ? ROW_STAGE4 : 1)];
     const int lane = threadIdx.x;
     const int base = blockIdx.x * 64;
     const int idx = base + lane;
@@ -143,20 +148,9 @@ __global__ void __launch_bounds__(64) preprocess_kernel(FwdParams p, GeometrySta
 
         // ---- 3D covariance (forward.cu:129-163) ----
         if (!PRECOMP) {
-            const float s0 = p.scale_modifier * sc0, s1 = p.scale_modifier * sc1, s2 = p.scale_modifier * sc2;
-            const float4 q = quat;
-            const float r = q.x, x = q.y, y = q.z, z = q.w;
-            // column-major R as filled by the reference (forward.cu:145-149); M[c][r] = s_r * R[c][r]
-            const float M00 = s0 * (1.f - 2.f * (y * y + z * z)), M01 = s1 * (2.f * (x * y - r * z)), M02 = s2 * (2.f * (x * z + r * y));
-            const float M10 = s0 * (2.f * (x * y + r * z)), M11 = s1 * (1.f - 2.f * (x * x + z * z)), M12 = s2 * (2.f * (y * z - r * x));
-            const float M20 = s0 * (2.f * (x * z - r * y)), M21 = s1 * (2.f * (y * z + r * x)), M22 = s2 * (1.f - 2.f * (x * x + y * y));
-            // Sigma[c][r] = M[r][0]*M[c][0] + M[r][1]*M[c][1] + M[r][2]*M[c][2]
-            c0 = M00 * M00 + M01 * M01 + M02 * M02;
-            c1 = M10 * M00 + M11 * M01 + M12 * M02;
-            c2 = M20 * M00 + M21 * M01 + M22 * M02;
-            c3 = M10 * M10 + M11 * M11 + M12 * M12;
-            c4 = M20 * M10 + M21 * M11 + M22 * M12;
-            c5 = M20 * M20 + M21 * M21 + M22 * M22;
+            float cv[6];
+            cov3d_from_scale_rot(p.scale_modifier, sc0, sc1, sc2, quat, cv);   // (wg_common.h: the backward kernel recomputes the same six floats)
+            c0 = cv[0]; c1 = cv[1]; c2 = cv[2]; c3 = cv[3]; c4 = cv[4]; c5 = cv[5];
             float* dst = g.cov3D + 6 * (size_t)idx;
             dst[0] = c0; dst[1] = c1; dst[2] = c2; dst[3] = c3; dst[4] = c4; dst[5] = c5;
         }
@@ -226,9 +220,10 @@ __global__ void __launch_bounds__(64) preprocess_kernel(FwdParams p, GeometrySta
 #undef WG_SH_STAGE
         __syncthreads();
     }
-    if (!inside) return;
-
-    if (vis) {
+    float row[BWD_ROW_FLOATS];   // ROW: zeros for a culled Gaussian
+#pragma unroll
+    for (int i = 0; i < BWD_ROW_FLOATS; i++) row[i] = 0.f;
+    if (vis) {   // (false for the out-of-range lanes of the last wave)
         float cr, cg, cb;
         float c2r = 0.f, c2g = 0.f, c2b = 0.f;   // second colour set (two-colour walk): precomputed, or the same SH block through a second tone
         bool two = false;                        // wave-uniform
@@ -261,6 +256,7 @@ __global__ void __launch_bounds__(64) preprocess_kernel(FwdParams p, GeometrySta
                 cr = sh_channel(p.D, sh + 0, dx, dy, dz);
                 cg = sh_channel(p.D, sh + 1, dx, dy, dz);
                 cb = sh_channel(p.D, sh + 2, dx, dy, dz);
+                if constexpr (ROW) bwd_row_terms<true>(p.D, sh, 16, px - camx, py - camy, pz - camz, row);
                 if constexpr (TONE) {
                     if (tone.second) {   // kernel argument: the same coefficients (still staged in LDS) through the second tone
                         float m[3], o[3], xin, t;
@@ -310,6 +306,7 @@ __global__ void __launch_bounds__(64) preprocess_kernel(FwdParams p, GeometrySta
                 cr = sh_channel(p.D, sh + 0, dx, dy, dz);
                 cg = sh_channel(p.D, sh + 1, dx, dy, dz);
                 cb = sh_channel(p.D, sh + 2, dx, dy, dz);
+                if constexpr (ROW) bwd_row_terms<false>(p.D, sh, p.M, px - camx, py - camy, pz - camz, row);
             }
             int flags = (cr < 0 ? 1 : 0) | (cg < 0 ? 2 : 0) | (cb < 0 ? 4 : 0);
             if (two) flags |= (c2r < 0 ? 8 : 0) | (c2g < 0 ? 16 : 0) | (c2b < 0 ? 32 : 0);   // (only the TONE instantiations can get here with two set)
@@ -331,6 +328,7 @@ __global__ void __launch_bounds__(64) preprocess_kernel(FwdParams p, GeometrySta
         const bool drawn = radius_i > 0;
         conx = drawn ? conx : 0.0f; cony = drawn ? cony : 0.0f; conz = drawn ? conz : 0.0f;
         const float o_eff = drawn ? opacity * coef : 0.0f;
+        row[9] = o_eff;
         float4* rec = g.splats + 3 * (size_t)idx;
         rec[0] = make_float4(pixx, pixy, conx, cony);
         if (two) {   // Two-colour walk: the second set rides in the record's three spare floats
@@ -343,12 +341,30 @@ __global__ void __launch_bounds__(64) preprocess_kernel(FwdParams p, GeometrySta
             rec[2] = make_float4(cg, cb, ext.x, ext.y);
         }
     }
-    // always written (all-zero for a culled Gaussian): the binning kernels read the rectangle only
-    g.rects[idx] = vis ? make_ushort4((unsigned short)rminx, (unsigned short)rminy, (unsigned short)rmaxx, (unsigned short)rmaxy)
-                       : make_ushort4(0, 0, 0, 0);
-    g.radii[idx] = radius_i;
-    if (radii_out) radii_out[idx] = radius_i;
-    g.tiles_touched[idx] = touched;
+    if (inside) {
+        // always written (all-zero for a culled Gaussian): the binning kernels read the rectangle only
+        g.rects[idx] = vis ? make_ushort4((unsigned short)rminx, (unsigned short)rminy, (unsigned short)rmaxx, (unsigned short)rmaxy)
+                           : make_ushort4(0, 0, 0, 0);
+        g.radii[idx] = radius_i;
+        if (radii_out) radii_out[idx] = radius_i;
+        g.tiles_touched[idx] = touched;
+    }
+    if constexpr (ROW) {
+        float* rs = reinterpret_cast<float*>(stage);
+        if (FAST_SH) __syncthreads();   // every lane has read its SH block out of the stage
+#pragma unroll
+        for (int i = 0; i < BWD_ROW_FLOATS; i++) rs[lane * BWD_ROW_FLOATS + i] = row[i];
+        __syncthreads();
+        // 40 bytes per row: the span starts 16-byte aligned (64 rows = 2560 bytes per wave) and holds a whole number of 8-byte pairs
+        const int npairs = min(64, p.P - base) * (BWD_ROW_FLOATS / 2);
+        float2* dst = reinterpret_cast<float2*>(g.bwd_row + (size_t)base * BWD_ROW_FLOATS);
+        const float2* src = reinterpret_cast<const float2*>(rs);
+#pragma unroll
+        for (int i = 0; i < BWD_ROW_FLOATS / 2; i++) {
+            const int f = i * 64 + lane;
+            if (f < npairs) dst[f] = src[f];
+        }
+    }
 }
 
 // The colour half of a split frame (GEOM_ONLY above): computeColorFromSH (forward.cu:20-71) with the operations, their order and the
@@ -357,7 +373,8 @@ __global__ void __launch_bounds__(64) preprocess_kernel(FwdParams p, GeometrySta
 // others, and only when some tile asked for its far instances (split->need_far, set by the first fix-up phase).  One Gaussian per lane, its
 // twelve 16-byte loads at a 192-byte stride: with one lane in ten active a wave touches a tenth of its block's lines (a coalesced block load
 // would fetch all of them for one near Gaussian in 64).
-template <bool FAR, bool VEC>
+// ROW: the direction terms of the Gaussian's backward row (preprocess_kernel's GEOM_ONLY instantiation left zeros and the combined opacity).
+template <bool FAR, bool VEC, bool ROW>
 __global__ void __launch_bounds__(256) sh_colour_kernel(FwdParams p, GeometryState g, const SplitState* __restrict__ split) {
     const uint32_t near_code = split->near_code;
     if (FAR && (split->need_far == 0u || near_code == SPLIT_OFF)) return;   // uniform: nobody asked
@@ -371,6 +388,7 @@ __global__ void __launch_bounds__(256) sh_colour_kernel(FwdParams p, GeometrySta
     const float len = sqrtf(dx * dx + dy * dy + dz * dz);
     dx = dx / len; dy = dy / len; dz = dz / len;
     float cr, cg, cb;
+    float row[9];
     if (VEC) {   // M == 16, 16-byte aligned
         const float4* src = reinterpret_cast<const float4*>(p.shs) + (size_t)idx * 12;
         float sh[48];
@@ -382,11 +400,18 @@ __global__ void __launch_bounds__(256) sh_colour_kernel(FwdParams p, GeometrySta
         cr = sh_channel(p.D, sh + 0, dx, dy, dz);
         cg = sh_channel(p.D, sh + 1, dx, dy, dz);
         cb = sh_channel(p.D, sh + 2, dx, dy, dz);
+        if constexpr (ROW) bwd_row_terms<true>(p.D, sh, 16, px - camx, py - camy, pz - camz, row);
     } else {
         const float* sh = p.shs + (size_t)idx * p.M * 3;
         cr = sh_channel(p.D, sh + 0, dx, dy, dz);
         cg = sh_channel(p.D, sh + 1, dx, dy, dz);
         cb = sh_channel(p.D, sh + 2, dx, dy, dz);
+        if constexpr (ROW) bwd_row_terms<false>(p.D, sh, p.M, px - camx, py - camy, pz - camz, row);
+    }
+    if constexpr (ROW) {   // (one lane in ten is active here: per-lane stores, like the record's colour floats below)
+        float* dst = g.bwd_row + (size_t)idx * BWD_ROW_FLOATS;
+#pragma unroll
+        for (int i = 0; i < 9; i++) dst[i] = row[i];
     }
     g.clamped[idx] = (unsigned char)((cr < 0 ? 1 : 0) | (cg < 0 ? 2 : 0) | (cb < 0 ? 4 : 0));
     float* rec = reinterpret_cast<float*>(g.splats + 3 * (size_t)idx);
@@ -395,14 +420,20 @@ __global__ void __launch_bounds__(256) sh_colour_kernel(FwdParams p, GeometrySta
     rec[9] = fmaxf(cb, 0.0f);
 }
 
-hipError_t launch_sh_colour(const FwdParams& p, const GeometryState& g, const SplitState* split, bool far, hipStream_t stream) {
+hipError_t launch_sh_colour(const FwdParams& p, const GeometryState& g, const SplitState* split, bool far, bool row, hipStream_t stream) {
     if (p.P <= 0) return hipSuccess;
     const bool vec = p.M == 16 && (reinterpret_cast<uintptr_t>(p.shs) % 16 == 0);
     const dim3 grid((p.P + 255) / 256), block(256);
-    if (far && vec) hipLaunchKernelGGL((sh_colour_kernel<true, true>), grid, block, 0, stream, p, g, split);
-    else if (far) hipLaunchKernelGGL((sh_colour_kernel<true, false>), grid, block, 0, stream, p, g, split);
-    else if (vec) hipLaunchKernelGGL((sh_colour_kernel<false, true>), grid, block, 0, stream, p, g, split);
-    else hipLaunchKernelGGL((sh_colour_kernel<false, false>), grid, block, 0, stream, p, g, split);
+#define WG_LAUNCH(F, V)                                                                                                      \
+    do {                                                                                                                     \
+        if (row) hipLaunchKernelGGL((sh_colour_kernel<F, V, true>), grid, block, 0, stream, p, g, split);                    \
+        else hipLaunchKernelGGL((sh_colour_kernel<F, V, false>), grid, block, 0, stream, p, g, split);                       \
+    } while (0)
+    if (far && vec) WG_LAUNCH(true, true);
+    else if (far) WG_LAUNCH(true, false);
+    else if (vec) WG_LAUNCH(false, true);
+    else WG_LAUNCH(false, false);
+#undef WG_LAUNCH
     return hipGetLastError();
 }
 
@@ -415,7 +446,8 @@ __global__ void __launch_bounds__(256) mark_visible_kernel(int P, const float* _
     present[idx] = !(vz <= 0.2f);  // auxiliary.h:154
 }
 
-hipError_t launch_preprocess(const FwdParams& p, const ShTone& tone_in, const GeometryState& g, int* radii_out, bool geom_only, hipStream_t stream) {
+// row: the frame carries backward rows (api.hip decides: plain SH colours, a backward call expected)
+hipError_t launch_preprocess(const FwdParams& p, const ShTone& tone_in, const GeometryState& g, int* radii_out, bool geom_only, bool row, hipStream_t stream) {
     if (p.P <= 0) return hipSuccess;
     const bool fast = p.shs != nullptr && p.colors_precomp == nullptr && p.M == 16 && (reinterpret_cast<uintptr_t>(p.shs) % 16 == 0);
     const bool pre = p.cov3D_precomp != nullptr;
@@ -423,11 +455,18 @@ hipError_t launch_preprocess(const FwdParams& p, const ShTone& tone_in, const Ge
     const bool tone = tone_in.enabled && p.shs != nullptr && p.colors_precomp == nullptr;
     if (geom_only) {   // (api.hip asks for it with plain SH colours only; launch_sh_colour supplies the colours)
         if (tone || p.shs == nullptr || p.colors_precomp != nullptr || p.colors_precomp2 != nullptr) return hipErrorInvalidValue;
-        if (pre) hipLaunchKernelGGL((preprocess_kernel<0, true, false, true>), grid, block, 0, stream, p, g, radii_out, NoTone{});
+        if (pre && row) hipLaunchKernelGGL((preprocess_kernel<0, true, false, true, true>), grid, block, 0, stream, p, g, radii_out, NoTone{});
+        else if (pre) hipLaunchKernelGGL((preprocess_kernel<0, true, false, true>), grid, block, 0, stream, p, g, radii_out, NoTone{});
+        else if (row) hipLaunchKernelGGL((preprocess_kernel<0, false, false, true, true>), grid, block, 0, stream, p, g, radii_out, NoTone{});
         else hipLaunchKernelGGL((preprocess_kernel<0, false, false, true>), grid, block, 0, stream, p, g, radii_out, NoTone{});
         return hipGetLastError();
     }
-#define WG_LAUNCH(F, C) hipLaunchKernelGGL((preprocess_kernel<F, C, false>), grid, block, 0, stream, p, g, radii_out, NoTone{})
+    if (row && (tone || p.shs == nullptr || p.colors_precomp != nullptr || p.colors_precomp2 != nullptr)) return hipErrorInvalidValue;
+#define WG_LAUNCH(F, C)                                                                                                                  \
+    do {                                                                                                                                 \
+        if (row) hipLaunchKernelGGL((preprocess_kernel<F, C, false, false, true>), grid, block, 0, stream, p, g, radii_out, NoTone{});   \
+        else hipLaunchKernelGGL((preprocess_kernel<F, C, false>), grid, block, 0, stream, p, g, radii_out, NoTone{});                    \
+    } while (0)
 #define WG_LAUNCH_TONE(F, C) hipLaunchKernelGGL((preprocess_kernel<F, C, true>), grid, block, 0, stream, p, g, radii_out, tone_in)
 #define WG_LAUNCH_FAST(L, C) do { if (p.nt_stream) L(2, C); else L(1, C); } while (0)
     if (tone) {

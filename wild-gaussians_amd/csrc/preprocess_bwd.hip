@@ -22,51 +22,51 @@
 
 namespace wg {
 
-constexpr float C0 = 0.28209479177387814f;
-constexpr float C1 = 0.4886025119029199f;
-constexpr float C2a = 1.0925484305920792f, C2b = -1.0925484305920792f, C2c = 0.31539156525252005f, C2d = -1.0925484305920792f,
-                C2e = 0.5462742152960396f;
-constexpr float C3a = -0.5900435899266435f, C3b = 2.890611442640554f, C3c = -0.4570457994644658f, C3d = 0.3731763325901154f,
-                C3e = -0.4570457994644658f, C3f = 1.445305721320277f, C3g = -0.5900435899266435f;
-
 constexpr int SH_PITCH4 = 13;  // float4 per Gaussian in LDS (12 used + 1 pad)
 
-// SH basis values B[k] and their derivatives w.r.t. the (unnormalised-looking) direction components, for the
-// polynomial of forward.cu:30-62; coefficients of degrees above `deg` are zeroed.
-__device__ __forceinline__ void sh_basis(int deg, float x, float y, float z, float* B, float* Dx, float* Dy, float* Dz) {
-    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-    const float m1 = deg > 0 ? 1.f : 0.f, m2 = deg > 1 ? 1.f : 0.f, m3 = deg > 2 ? 1.f : 0.f;
-    B[0] = C0; Dx[0] = 0.f; Dy[0] = 0.f; Dz[0] = 0.f;
-    B[1] = m1 * -C1 * y; Dx[1] = 0.f; Dy[1] = m1 * -C1; Dz[1] = 0.f;
-    B[2] = m1 * C1 * z; Dx[2] = 0.f; Dy[2] = 0.f; Dz[2] = m1 * C1;
-    B[3] = m1 * -C1 * x; Dx[3] = m1 * -C1; Dy[3] = 0.f; Dz[3] = 0.f;
-    B[4] = m2 * C2a * xy; Dx[4] = m2 * C2a * y; Dy[4] = m2 * C2a * x; Dz[4] = 0.f;
-    B[5] = m2 * C2b * yz; Dx[5] = 0.f; Dy[5] = m2 * C2b * z; Dz[5] = m2 * C2b * y;
-    B[6] = m2 * C2c * (2.f * zz - xx - yy); Dx[6] = m2 * C2c * -2.f * x; Dy[6] = m2 * C2c * -2.f * y; Dz[6] = m2 * C2c * 4.f * z;
-    B[7] = m2 * C2d * xz; Dx[7] = m2 * C2d * z; Dy[7] = 0.f; Dz[7] = m2 * C2d * x;
-    B[8] = m2 * C2e * (xx - yy); Dx[8] = m2 * C2e * 2.f * x; Dy[8] = m2 * C2e * -2.f * y; Dz[8] = 0.f;
-    B[9] = m3 * C3a * y * (3.f * xx - yy); Dx[9] = m3 * C3a * 6.f * xy; Dy[9] = m3 * C3a * 3.f * (xx - yy); Dz[9] = 0.f;
-    B[10] = m3 * C3b * xy * z; Dx[10] = m3 * C3b * yz; Dy[10] = m3 * C3b * xz; Dz[10] = m3 * C3b * xy;
-    B[11] = m3 * C3c * y * (4.f * zz - xx - yy); Dx[11] = m3 * C3c * -2.f * xy; Dy[11] = m3 * C3c * (-3.f * yy + 4.f * zz - xx);
-    Dz[11] = m3 * C3c * 8.f * yz;
-    B[12] = m3 * C3d * z * (2.f * zz - 3.f * xx - 3.f * yy); Dx[12] = m3 * C3d * -6.f * xz; Dy[12] = m3 * C3d * -6.f * yz;
-    Dz[12] = m3 * C3d * 3.f * (2.f * zz - xx - yy);
-    B[13] = m3 * C3e * x * (4.f * zz - xx - yy); Dx[13] = m3 * C3e * (-3.f * xx + 4.f * zz - yy); Dy[13] = m3 * C3e * -2.f * xy;
-    Dz[13] = m3 * C3e * 8.f * xz;
-    B[14] = m3 * C3f * z * (xx - yy); Dx[14] = m3 * C3f * 2.f * xz; Dy[14] = m3 * C3f * -2.f * yz; Dz[14] = m3 * C3f * (xx - yy);
-    B[15] = m3 * C3g * x * (xx - 3.f * yy); Dx[15] = m3 * C3g * 3.f * (xx - yy); Dy[15] = m3 * C3g * -6.f * xy; Dz[15] = 0.f;
+// (sh_basis, sh_basis_exact: wg_common.h)
+
+// The row instantiations' SH part, without fused multiply-adds: every one of them (16-coefficient or generic layout, with or without scales)
+// then gives the same bits, whatever the code around it lets the compiler contract.
+struct ViewDir { float ox, oy, oz, sum2, ilen; };
+__device__ __forceinline__ ViewDir view_dir(float mx, float my, float mz, float camx, float camy, float camz) {
+#pragma clang fp contract(off)
+    ViewDir d;
+    d.ox = mx - camx; d.oy = my - camy; d.oz = mz - camz;
+    d.sum2 = d.ox * d.ox + d.oy * d.oy + d.oz * d.oz;
+    d.ilen = 1.0f / sqrtf(d.sum2);
+    return d;
+}
+// dL_ddir = sum_ch T[ch][.] * dL_dRGB[ch] from the row's direction terms, then dnormvdv (auxiliary.h:107-117) into dL_dmean3D
+__device__ __forceinline__ void row_dir_backward(float2 r0, float2 r1, float2 r2, float2 r3, float t22, const float* dRGB, const ViewDir& d,
+                                                 float& gmx, float& gmy, float& gmz) {
+#pragma clang fp contract(off)
+    const float ddx = r0.x * dRGB[0] + r1.y * dRGB[1] + r3.x * dRGB[2];
+    const float ddy = r0.y * dRGB[0] + r2.x * dRGB[1] + r3.y * dRGB[2];
+    const float ddz = r1.x * dRGB[0] + r2.y * dRGB[1] + t22 * dRGB[2];
+    const float ox = d.ox, oy = d.oy, oz = d.oz, sum2 = d.sum2;
+    const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
+    gmx = gmx + ((sum2 - ox * ox) * ddx - oy * ox * ddy - oz * ox * ddz) * invsum32;
+    gmy = gmy + (-ox * oy * ddx + (sum2 - oy * oy) * ddy - oz * oy * ddz) * invsum32;
+    gmz = gmz + (-ox * oz * ddx - oy * oz * ddy + (sum2 - oz * oz) * ddz) * invsum32;
 }
 
 // Load schedule: the memory counter retires in issue order, so every per-Gaussian input is requested first, the
 // 12 KiB SH block second (into registers), and only the SH part of the arithmetic -- placed last -- waits for it.
 // RECORD: the per-tile pass left its raw sums in grad_rec (wg_common.h: GRAD_REC_*); this kernel applies the per-Gaussian factors
 // and WRITES dL_dmean2D / dL_dconic / dL_dopacity / dL_dcolor for every Gaussian.  !RECORD: those four arrive accumulated.
-template <int SH_MODE, bool HAS_SCALES, bool TONE, bool RECORD>   // SH_MODE: 0 generic layout, 1 coalesced blocks through LDS, 2 the same with non-temporal accesses
+// ROW (plain SH colours, the forward pass left backward rows: wg_common.h, BWD_ROW_FLOATS): the SH block is not read at all -- dL_dsh needs
+// no coefficient and dL_ddir comes from the row's nine direction terms -- and the combined opacity is the row's tenth float instead of one
+// float of the splat record's 48-byte line.  RECOMP (ROW with scales and no precomputed covariance): the six covariance floats are recomputed
+// from the scales and the rotation the kernel loads anyway (cov3d_from_scale_rot: the forward kernel's bits) instead of read back.
+template <int SH_MODE, bool HAS_SCALES, bool TONE, bool RECORD, bool ROW = false, bool RECOMP = false>   // SH_MODE: 0 generic layout, 1 coalesced blocks through LDS, 2 the same with non-temporal accesses
 __global__ void __launch_bounds__(64) preprocess_backward_kernel(
     BwdParams p, const float4* __restrict__ splats, const unsigned char* __restrict__ clamped, const float4* __restrict__ grad_rec,
     float* __restrict__ dL_dmean2D, float* __restrict__ dL_dconic, float* __restrict__ dL_dopacity,
     float* __restrict__ dL_dcolor, float* __restrict__ dL_dmean3D, float* __restrict__ dL_dcov3D,
     float* __restrict__ dL_dsh, float* __restrict__ dL_dscale, float* __restrict__ dL_drot, ToneArg<TONE> tone) {
+    static_assert(!ROW || !TONE, "toned frames carry no backward row");
+    static_assert(!RECOMP || (ROW && HAS_SCALES), "the covariance is recomputed from scales and rotations");
     constexpr bool FAST_SH = SH_MODE != 0, NT = SH_MODE == 2;
     __shared__ float4 stage[FAST_SH ? 64 * SH_PITCH4 : 1];
     const int lane = threadIdx.x;
@@ -88,10 +88,21 @@ __global__ void __launch_bounds__(64) preprocess_backward_kernel(
     // (non-const: they are operands of the ordering fence below, which keeps the compiler from sinking the loads)
     int radius = p.radii[ld];
     float mx = p.means3D[3 * ld], my = p.means3D[3 * ld + 1], mz = p.means3D[3 * ld + 2];
-    const float* cv = p.cov3D + 6 * (size_t)ld;
-    float v0 = cv[0], v1 = cv[1], v2 = cv[2], v3 = cv[3], v4 = cv[4], v5 = cv[5];
+    float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f, v4 = 0.f, v5 = 0.f;
+    if constexpr (!RECOMP) {
+        const float* cv = p.cov3D + 6 * (size_t)ld;
+        v0 = cv[0]; v1 = cv[1]; v2 = cv[2]; v3 = cv[3]; v4 = cv[4]; v5 = cv[5];
+    }
     float4 dconic;
-    float combined_opacity = splats[3 * (size_t)ld + 1].y;
+    float combined_opacity;
+    float2 rw0 = make_float2(0.f, 0.f), rw1 = rw0, rw2 = rw0, rw3 = rw0, rw4 = rw0;   // ROW: T[0][xyz] T[1][xyz] T[2][xyz] | combined opacity
+    if constexpr (ROW) {
+        const float2* rp = reinterpret_cast<const float2*>(p.bwd_row + (size_t)ld * BWD_ROW_FLOATS);
+        rw0 = rp[0]; rw1 = rp[1]; rw2 = rp[2]; rw3 = rp[3]; rw4 = rp[4];
+        combined_opacity = rw4.y;
+    } else {
+        combined_opacity = splats[3 * (size_t)ld + 1].y;
+    }
     float dLdo_in, g2x, g2y, g2abs = 0.f, dcol0, dcol1, dcol2;
     if (RECORD) {
         const float4 r0 = grad_rec[3 * (size_t)ld], r1 = grad_rec[3 * (size_t)ld + 1], r2 = grad_rec[3 * (size_t)ld + 2];
@@ -118,7 +129,7 @@ __global__ void __launch_bounds__(64) preprocess_backward_kernel(
     __builtin_amdgcn_sched_barrier(0);  // the machine scheduler would otherwise slip some of the loads above behind the SH ones
     float4 sr0, sr1, sr2, sr3, sr4, sr5, sr6, sr7, sr8, sr9, sr10, sr11;
     sr0 = sr1 = sr2 = sr3 = sr4 = sr5 = sr6 = sr7 = sr8 = sr9 = sr10 = sr11 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (FAST_SH) {  // 64 Gaussians x 12 float4, coalesced
+    if (FAST_SH && !ROW) {  // 64 Gaussians x 12 float4, coalesced
         const float4* src = reinterpret_cast<const float4*>(p.shs) + (size_t)base * 12;
         const int last = min(64, p.P - base) * 12 - 1;
 #define WG_SH_LOAD(i) sr##i = stream_load4<NT>(&src[min(i * 64 + lane, last)]);
@@ -133,6 +144,8 @@ __global__ void __launch_bounds__(64) preprocess_backward_kernel(
                    "+v"(dcol2), "+v"(q.x), "+v"(q.y), "+v"(q.z), "+v"(q.w), "+v"(sc0), "+v"(sc1), "+v"(sc2), "+v"(radius), "+v"(raw_op), "+v"(filt)
                  :
                  : "memory");
+    if constexpr (ROW)
+        asm volatile("" : "+v"(rw0.x), "+v"(rw0.y), "+v"(rw1.x), "+v"(rw1.y), "+v"(rw2.x), "+v"(rw2.y), "+v"(rw3.x), "+v"(rw3.y), "+v"(rw4.x) : : "memory");
     // raw-parameter mode: what the forward kernel made of the raw parameters, recomputed (nothing was saved); the gradients of the
     // activated values are turned into those of the raw ones where they are written, below
     const bool raw_mode = HAS_SCALES && p.filter_3D != nullptr;   // wave-uniform
@@ -141,6 +154,11 @@ __global__ void __launch_bounds__(64) preprocess_backward_kernel(
         act = act_forward(q, sc0, sc1, sc2, raw_op, filt);
         q = act.q;
         sc0 = act.sc[0]; sc1 = act.sc[1]; sc2 = act.sc[2];
+    }
+    if constexpr (RECOMP) {   // (of the activated values in raw-parameter mode, as in the forward kernel)
+        float cvr[6];
+        cov3d_from_scale_rot(p.scale_modifier, sc0, sc1, sc2, q, cvr);
+        v0 = cvr[0]; v1 = cvr[1]; v2 = cvr[2]; v3 = cvr[3]; v4 = cvr[4]; v5 = cvr[5];
     }
     const bool vis = in && radius > 0;
     if (RECORD) {
@@ -326,7 +344,7 @@ __global__ void __launch_bounds__(64) preprocess_backward_kernel(
     }
 
     asm volatile("" : "+v"(gmx), "+v"(gmy), "+v"(gmz) : : "memory");  // the SH part stays below the geometry part
-    if (FAST_SH) {
+    if (FAST_SH && !ROW) {
         const int nvalid = min(64, p.P - base) * 12;
 #define WG_SH_STAGE(i)                                                          \
     {                                                                           \
@@ -348,11 +366,17 @@ __global__ void __launch_bounds__(64) preprocess_backward_kernel(
         for (int k = 0; k < 48; k++) dsh[k] = 0.f;
     }
     if (vis && p.shs != nullptr) {
-        const float ox = mx - camx, oy = my - camy, oz = mz - camz;
-        const float sum2 = ox * ox + oy * oy + oz * oz;
-        const float ilen = 1.0f / sqrtf(sum2);
+        float ox = mx - camx, oy = my - camy, oz = mz - camz;
+        float sum2 = ox * ox + oy * oy + oz * oz;
+        float ilen = 1.0f / sqrtf(sum2);
+        ViewDir vd{};
+        if constexpr (ROW) {
+            vd = view_dir(mx, my, mz, camx, camy, camz);
+            ox = vd.ox; oy = vd.oy; oz = vd.oz; sum2 = vd.sum2; ilen = vd.ilen;
+        }
         float B[16], Dx[16], Dy[16], Dz[16];
-        sh_basis(p.D, ox * ilen, oy * ilen, oz * ilen, B, Dx, Dy, Dz);
+        if constexpr (ROW) sh_basis_exact(p.D, ox * ilen, oy * ilen, oz * ilen, B, Dx, Dy, Dz);
+        else sh_basis(p.D, ox * ilen, oy * ilen, oz * ilen, B, Dx, Dy, Dz);
         const float dRGB[3] = {(cl & 1) ? 0.f : dcol0, (cl & 2) ? 0.f : dcol1, (cl & 4) ? 0.f : dcol2};
         float ddx = 0.f, ddy = 0.f, ddz = 0.f;  // dL_ddir
         // TONE with a second set (ShTone::second): the same coefficients fed a second colour through tone 2; its dL/dRGB are the record's
@@ -382,7 +406,28 @@ __global__ void __launch_bounds__(64) preprocess_backward_kernel(
                 if (tone.offset) to[ch] = tone.offset[3 * idx + ch];
             }
         }
-        if (FAST_SH) {
+        if constexpr (ROW) {
+            // dL_ddir = sum_ch T[ch][.] * dL_dRGB[ch] with the forward pass's T; dL_dsh[k][ch] = B[k] * dL_dRGB[ch] needs no coefficient.
+            // (a Gaussian the forward pass never coloured -- lazy colour, far and never asked for -- has a zero row and a zero dL_dRGB)
+            row_dir_backward(rw0, rw1, rw2, rw3, rw4.x, dRGB, vd, gmx, gmy, gmz);
+            if (FAST_SH) {
+#pragma unroll
+                for (int k = 0; k < 16; k++)
+#pragma unroll
+                    for (int ch = 0; ch < 3; ch++) dsh[3 * k + ch] = B[k] * dRGB[ch];
+            } else {
+                float* d = dL_dsh + (size_t)idx * p.M * 3;
+                const int ncoef = (p.D + 1) * (p.D + 1);
+                for (int k = 0; k < p.M; k++) {
+                    float bk = 0.f;   // (a dynamic index would send B to scratch)
+#pragma unroll
+                    for (int j = 0; j < 16; j++)
+                        if (j == k && k < ncoef) bk = B[j];
+#pragma unroll
+                    for (int ch = 0; ch < 3; ch++) d[3 * k + ch] = bk * dRGB[ch];
+                }
+            }
+        } else if (FAST_SH) {
             float sh[48];
 #pragma unroll
             for (int qd = 0; qd < 12; qd++) {
@@ -467,11 +512,13 @@ __global__ void __launch_bounds__(64) preprocess_backward_kernel(
                     ddz += dzk * w;
                 }
         }
-        // dnormvdv, auxiliary.h:107-117
-        const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
-        gmx += ((sum2 - ox * ox) * ddx - oy * ox * ddy - oz * ox * ddz) * invsum32;
-        gmy += (-ox * oy * ddx + (sum2 - oy * oy) * ddy - oz * oy * ddz) * invsum32;
-        gmz += (-ox * oz * ddx - oy * oz * ddy + (sum2 - oz * oz) * ddz) * invsum32;
+        if constexpr (!ROW) {
+            // dnormvdv, auxiliary.h:107-117
+            const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
+            gmx += ((sum2 - ox * ox) * ddx - oy * ox * ddy - oz * ox * ddz) * invsum32;
+            gmy += (-ox * oy * ddx + (sum2 - oy * oy) * ddy - oz * oy * ddz) * invsum32;
+            gmz += (-ox * oz * ddx - oy * oz * ddy + (sum2 - oz * oz) * ddz) * invsum32;
+        }
     }
 
     // ---- outputs: written for every Gaussian of the range (zeros when culled) ----
@@ -520,6 +567,10 @@ hipError_t launch_preprocess_backward(const BwdParams& p, const ShTone& tone_in,
     const bool sc = p.scales != nullptr;
     const bool tone = tone_in.enabled && p.shs != nullptr;
     const float4* rec = reinterpret_cast<const float4*>(g.grad_rec);
+    const bool row = p.bwd_row != nullptr;   // (api.hip: the frame's forward call left rows and this call's arguments are plain SH colours)
+    if (row && (tone || p.shs == nullptr)) return hipErrorInvalidValue;
+    const bool recomp = row && sc && p.cov3D == nullptr;
+    if (!recomp && p.cov3D == nullptr) return hipErrorInvalidValue;
 #define WG_ARGS p, g.splats, g.clamped, rec, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot
 #define WG_LAUNCH(F, S)                                                                                                              \
     do {                                                                                                                             \
@@ -528,10 +579,26 @@ hipError_t launch_preprocess_backward(const BwdParams& p, const ShTone& tone_in,
         else if (record) hipLaunchKernelGGL((preprocess_backward_kernel<F, S, false, true>), grid, block, 0, stream, WG_ARGS, NoTone{});    \
         else hipLaunchKernelGGL((preprocess_backward_kernel<F, S, false, false>), grid, block, 0, stream, WG_ARGS, NoTone{});               \
     } while (0)
-    if (fast && sc) { if (p.nt_stream) WG_LAUNCH(2, true); else WG_LAUNCH(1, true); }
+#define WG_LAUNCH_ROW(F, S, C)                                                                                                                    \
+    do {                                                                                                                                          \
+        if (record) hipLaunchKernelGGL((preprocess_backward_kernel<F, S, false, true, true, C>), grid, block, 0, stream, WG_ARGS, NoTone{});      \
+        else hipLaunchKernelGGL((preprocess_backward_kernel<F, S, false, false, true, C>), grid, block, 0, stream, WG_ARGS, NoTone{});            \
+    } while (0)
+#define WG_LAUNCH_ROW_SC(F)                                                                                                                       \
+    do {                                                                                                                                          \
+        if (recomp) WG_LAUNCH_ROW(F, true, true); else if (sc) WG_LAUNCH_ROW(F, true, false); else WG_LAUNCH_ROW(F, false, false);                \
+    } while (0)
+    if (row) {
+        if (fast && p.nt_stream) WG_LAUNCH_ROW_SC(2);
+        else if (fast) WG_LAUNCH_ROW_SC(1);
+        else WG_LAUNCH_ROW_SC(0);
+    }
+    else if (fast && sc) { if (p.nt_stream) WG_LAUNCH(2, true); else WG_LAUNCH(1, true); }
     else if (fast) { if (p.nt_stream) WG_LAUNCH(2, false); else WG_LAUNCH(1, false); }
     else if (sc) WG_LAUNCH(0, true);
     else WG_LAUNCH(0, false);
+#undef WG_LAUNCH_ROW_SC
+#undef WG_LAUNCH_ROW
 #undef WG_LAUNCH
 #undef WG_ARGS
     return hipGetLastError();

@@ -124,7 +124,7 @@ struct ForwardResult {
 
 ForwardResult forward(const Scene& s, const torch::Tensor& opacity, const int H, const int W, const bool prefiltered, const py::object& sh_tone,
                       const py::object& binning_capacity, const OptTensor& colors2, const OptTensor& filter_3D, const py::object& sh_second,
-                      const wg_call_options& co) {
+                      const wg_call_options& co, const bool forward_only = false) {
     if (s.means3D.ndimension() != 2 || s.means3D.size(1) != 3) AT_ERROR("means3D must have dimensions (num_points, 3)");   // rasterize_points.cu:59-61
     if (!s.means3D.is_cuda()) throw std::runtime_error("means3D must live on a HIP device: this rasterizer has no CPU path");
     const auto dev = s.means3D.device();
@@ -170,6 +170,7 @@ ForwardResult forward(const Scene& s, const torch::Tensor& opacity, const int H,
     a.image_alloc = resize_cb; a.image_user = &r.img;
     a.prefiltered = prefiltered; a.opacities = ptr(op); a.out_color = r.color.data_ptr<float>(); a.radii = r.radii.data_ptr<int>();
     a.binning_capacity = capacity;
+    a.forward_only = forward_only ? 1 : 0;
     if (tone.given) a.tone = &tone.t;
     wg_second_image second{};
     torch::Tensor c2;
@@ -364,13 +365,25 @@ py::tuple RasterizeGaussiansEx(const torch::Tensor& background, const torch::Ten
                                const float kernel_size, const OptTensor& subpixel_offset, const int image_height, const int image_width,
                                const torch::Tensor& sh, const int degree, const torch::Tensor& campos, const bool prefiltered, const bool debug,
                                const py::object& sh_tone, const py::object& binning_capacity, const OptTensor& colors2, const OptTensor& filter_3D,
-                               const py::object& sh_second, const std::tuple<int, int, int>& options) {
+                               const py::object& sh_second, const std::tuple<int, int, int>& options, const bool forward_only) {
     const Scene s{background, means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, kernel_size,
                   opt(subpixel_offset), sh, degree, campos, debug};
     const ForwardResult r = forward(s, opacity, image_height, image_width, prefiltered, sh_tone, binning_capacity, colors2, filter_3D, sh_second,
-                                    call_options(options));
+                                    call_options(options), forward_only);
     if (r.color2.defined()) return py::make_tuple(r.rendered, r.color, r.radii, r.geom, r.binning, r.img, r.color2);
     return py::make_tuple(r.rendered, r.color, r.radii, r.geom, r.binning, r.img);
+}
+// (callers from before wg_forward_args::forward_only: a backward call may follow)
+py::tuple RasterizeGaussiansExNoHint(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors, const torch::Tensor& opacity,
+                                     const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier, const torch::Tensor& cov3D_precomp,
+                                     const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
+                                     const float kernel_size, const OptTensor& subpixel_offset, const int image_height, const int image_width,
+                                     const torch::Tensor& sh, const int degree, const torch::Tensor& campos, const bool prefiltered, const bool debug,
+                                     const py::object& sh_tone, const py::object& binning_capacity, const OptTensor& colors2, const OptTensor& filter_3D,
+                                     const py::object& sh_second, const std::tuple<int, int, int>& options) {
+    return RasterizeGaussiansEx(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
+                                kernel_size, subpixel_offset, image_height, image_width, sh, degree, campos, prefiltered, debug, sh_tone, binning_capacity,
+                                colors2, filter_3D, sh_second, options, false);
 }
 
 // -> the reference's eight, + (mul, offset, mul2, offset2) with sh_second, + dL_dcolors2 with a second colour set, + (mul, offset) with sh_tone
@@ -418,7 +431,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {   // ext.cpp:15-19
     m.def("rasterize_gaussians", &RasterizeGaussiansHIP);
     m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackwardHIP);
     m.def("mark_visible", &markVisible);
-    m.def("rasterize_gaussians_ex", &RasterizeGaussiansEx);                    // + the blocks of wg_forward_args
+    m.def("rasterize_gaussians_ex", &RasterizeGaussiansEx);                    // + the blocks of wg_forward_args, + the forward_only hint
+    m.def("rasterize_gaussians_ex", &RasterizeGaussiansExNoHint);              //   (overload without the hint)
     m.def("rasterize_gaussians_backward_ex", &RasterizeGaussiansBackwardEx);   // + the blocks of wg_backward_args
     m.def("rasterize_gaussians_backward_colour", &RasterizeGaussiansBackwardColour);   // wg_backward_args::colour_gradients_only
 }

@@ -35,9 +35,12 @@ struct GeometryState {
                           // grad_rec + 12 P: P more floats, the two-colour walk's thirteenth sum (render_bwd.hip: DUAL)
     char* scan_temp;
     size_t scan_temp_bytes;
+    float* bwd_row;  // rows only: BWD_ROW_FLOATS per Gaussian (below), written by the forward kernels of plain-SH frames that expect a backward
+                     // call.  Carved behind everything the other frames have (their buffers and offsets are what they were), in front of the
+                     // band lists, which only the forward call that decides both addresses.
     // band_lists: whether the two band-list arrays exist.  They are carved LAST, so that everything the backward pass and the
     // views address has the same offset either way (the decision is the forward call's alone, taken from its option snapshot).
-    static GeometryState fromChunk(char*& chunk, size_t P, bool band_lists);
+    static GeometryState fromChunk(char*& chunk, size_t P, bool band_lists, bool rows = false);
     static bool band_lists_possible(size_t P);  // chunk-local indices are 16-bit
 };
 
@@ -92,6 +95,113 @@ __device__ __forceinline__ void stream_store4(float4* p, float4 v) {
     } else {
         *p = v;
     }
+}
+
+// SH basis values B[k] and their derivatives w.r.t. the (unnormalised-looking) direction components, for the
+// polynomial of forward.cu:30-62; coefficients of degrees above `deg` are zeroed.  One text, two functions: sh_basis is what the
+// per-Gaussian backward kernel has always called, under its file's default contraction (the row-less instantiations keep their bits);
+// sh_basis_exact has no fused multiply-adds, whatever the flags of the file that includes it: the forward kernels (backward row, below) and
+// the row instantiations of the backward kernel get the same bits from it.
+#define WG_SH_BASIS_BODY \
+    constexpr float C0 = 0.28209479177387814f;                                                                                                         \
+    constexpr float C1 = 0.4886025119029199f;                                                                                                          \
+    constexpr float C2a = 1.0925484305920792f, C2b = -1.0925484305920792f, C2c = 0.31539156525252005f, C2d = -1.0925484305920792f,                     \
+    C2e = 0.5462742152960396f;                                                                                                                         \
+    constexpr float C3a = -0.5900435899266435f, C3b = 2.890611442640554f, C3c = -0.4570457994644658f, C3d = 0.3731763325901154f,                       \
+    C3e = -0.4570457994644658f, C3f = 1.445305721320277f, C3g = -0.5900435899266435f;                                                                  \
+    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;                                                                \
+    const float m1 = deg > 0 ? 1.f : 0.f, m2 = deg > 1 ? 1.f : 0.f, m3 = deg > 2 ? 1.f : 0.f;                                                          \
+    B[0] = C0; Dx[0] = 0.f; Dy[0] = 0.f; Dz[0] = 0.f;                                                                                                  \
+    B[1] = m1 * -C1 * y; Dx[1] = 0.f; Dy[1] = m1 * -C1; Dz[1] = 0.f;                                                                                   \
+    B[2] = m1 * C1 * z; Dx[2] = 0.f; Dy[2] = 0.f; Dz[2] = m1 * C1;                                                                                     \
+    B[3] = m1 * -C1 * x; Dx[3] = m1 * -C1; Dy[3] = 0.f; Dz[3] = 0.f;                                                                                   \
+    B[4] = m2 * C2a * xy; Dx[4] = m2 * C2a * y; Dy[4] = m2 * C2a * x; Dz[4] = 0.f;                                                                     \
+    B[5] = m2 * C2b * yz; Dx[5] = 0.f; Dy[5] = m2 * C2b * z; Dz[5] = m2 * C2b * y;                                                                     \
+    B[6] = m2 * C2c * (2.f * zz - xx - yy); Dx[6] = m2 * C2c * -2.f * x; Dy[6] = m2 * C2c * -2.f * y; Dz[6] = m2 * C2c * 4.f * z;                      \
+    B[7] = m2 * C2d * xz; Dx[7] = m2 * C2d * z; Dy[7] = 0.f; Dz[7] = m2 * C2d * x;                                                                     \
+    B[8] = m2 * C2e * (xx - yy); Dx[8] = m2 * C2e * 2.f * x; Dy[8] = m2 * C2e * -2.f * y; Dz[8] = 0.f;                                                 \
+    B[9] = m3 * C3a * y * (3.f * xx - yy); Dx[9] = m3 * C3a * 6.f * xy; Dy[9] = m3 * C3a * 3.f * (xx - yy); Dz[9] = 0.f;                               \
+    B[10] = m3 * C3b * xy * z; Dx[10] = m3 * C3b * yz; Dy[10] = m3 * C3b * xz; Dz[10] = m3 * C3b * xy;                                                 \
+    B[11] = m3 * C3c * y * (4.f * zz - xx - yy); Dx[11] = m3 * C3c * -2.f * xy; Dy[11] = m3 * C3c * (-3.f * yy + 4.f * zz - xx);                       \
+    Dz[11] = m3 * C3c * 8.f * yz;                                                                                                                      \
+    B[12] = m3 * C3d * z * (2.f * zz - 3.f * xx - 3.f * yy); Dx[12] = m3 * C3d * -6.f * xz; Dy[12] = m3 * C3d * -6.f * yz;                             \
+    Dz[12] = m3 * C3d * 3.f * (2.f * zz - xx - yy);                                                                                                    \
+    B[13] = m3 * C3e * x * (4.f * zz - xx - yy); Dx[13] = m3 * C3e * (-3.f * xx + 4.f * zz - yy); Dy[13] = m3 * C3e * -2.f * xy;                       \
+    Dz[13] = m3 * C3e * 8.f * xz;                                                                                                                      \
+    B[14] = m3 * C3f * z * (xx - yy); Dx[14] = m3 * C3f * 2.f * xz; Dy[14] = m3 * C3f * -2.f * yz; Dz[14] = m3 * C3f * (xx - yy);                      \
+    B[15] = m3 * C3g * x * (xx - 3.f * yy); Dx[15] = m3 * C3g * 3.f * (xx - yy); Dy[15] = m3 * C3g * -6.f * xy; Dz[15] = 0.f;
+__device__ __forceinline__ void sh_basis(int deg, float x, float y, float z, float* B, float* Dx, float* Dy, float* Dz) {
+    WG_SH_BASIS_BODY
+}
+__device__ __forceinline__ void sh_basis_exact(int deg, float x, float y, float z, float* B, float* Dx, float* Dy, float* Dz) {
+#pragma clang fp contract(off)
+    WG_SH_BASIS_BODY
+}
+#undef WG_SH_BASIS_BODY
+
+// Backward row (GeometryState::bwd_row): what the per-Gaussian backward kernel needs of the SH block and of the splat record, left by the
+// forward kernels that evaluate plain SH colours -- ten floats instead of the 192-byte block and the record's 48-byte line.
+//   row[3 ch + axis] = T[ch][axis] = sum_k D_axis[k] * sh[k][ch], k ascending (dL_ddir = sum_ch T[ch][.] * dL_dRGB[ch]);  row[9] = combined opacity
+constexpr int BWD_ROW_FLOATS = 10;
+// sh: coefficient k of channel ch at sh[3 k + ch]; ncoef: how many there are (M); the direction is (mean - campos) / |.|, formed as the
+// backward kernel forms it.  Same bits from every caller: no contraction, every term of the sums one explicit fused multiply-add (K = 16
+// unrolls over registers and leaves out the derivatives that are zero for every direction -- fma(0, v, T) = T --, otherwise a loop over memory).
+template <bool FIXED16>
+__device__ __forceinline__ void bwd_row_terms(int deg, const float* sh, int ncoef, float ox, float oy, float oz, float* T) {
+#pragma clang fp contract(off)
+    const float sum2 = ox * ox + oy * oy + oz * oz;
+    const float ilen = 1.0f / sqrtf(sum2);
+    float B[16], Dx[16], Dy[16], Dz[16];
+    sh_basis_exact(deg, ox * ilen, oy * ilen, oz * ilen, B, Dx, Dy, Dz);
+#pragma unroll
+    for (int i = 0; i < 9; i++) T[i] = 0.f;
+    if (FIXED16) {
+        constexpr unsigned NZX = 0xffffu & ~0x0027u, NZY = 0xffffu & ~0x008du, NZZ = 0xffffu & ~0x831bu;   // sh_basis: Dx[k] == 0 for k in {0,1,2,5}, ...
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) {
+                const float v = sh[3 * k + ch];
+                if ((NZX >> k) & 1u) T[3 * ch] = __fmaf_rn(Dx[k], v, T[3 * ch]);
+                if ((NZY >> k) & 1u) T[3 * ch + 1] = __fmaf_rn(Dy[k], v, T[3 * ch + 1]);
+                if ((NZZ >> k) & 1u) T[3 * ch + 2] = __fmaf_rn(Dz[k], v, T[3 * ch + 2]);
+            }
+    } else {
+        const int n = ncoef < 16 ? ncoef : 16;
+        for (int k = 0; k < n; k++) {
+            // (a dynamic index into the three derivative arrays would send them to scratch)
+            float dxk = 0.f, dyk = 0.f, dzk = 0.f;
+#pragma unroll
+            for (int j = 0; j < 16; j++)
+                if (j == k) { dxk = Dx[j]; dyk = Dy[j]; dzk = Dz[j]; }
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) {
+                const float v = sh[3 * k + ch];
+                T[3 * ch] = __fmaf_rn(dxk, v, T[3 * ch]);
+                T[3 * ch + 1] = __fmaf_rn(dyk, v, T[3 * ch + 1]);
+                T[3 * ch + 2] = __fmaf_rn(dzk, v, T[3 * ch + 2]);
+            }
+        }
+    }
+}
+
+// 3-D covariance from scale and rotation (forward.cu:129-163): the six floats the forward kernel stores, recomputed by the backward
+// kernel's row instantiations with the same operations in the same order (no contraction in either) -- the same bits.
+__device__ __forceinline__ void cov3d_from_scale_rot(float scale_modifier, float sc0, float sc1, float sc2, float4 q, float* c) {
+#pragma clang fp contract(off)
+    const float s0 = scale_modifier * sc0, s1 = scale_modifier * sc1, s2 = scale_modifier * sc2;
+    const float r = q.x, x = q.y, y = q.z, z = q.w;
+    // column-major R as filled by the reference (forward.cu:145-149); M[c][r] = s_r * R[c][r]
+    const float M00 = s0 * (1.f - 2.f * (y * y + z * z)), M01 = s1 * (2.f * (x * y - r * z)), M02 = s2 * (2.f * (x * z + r * y));
+    const float M10 = s0 * (2.f * (x * y + r * z)), M11 = s1 * (1.f - 2.f * (x * x + z * z)), M12 = s2 * (2.f * (y * z - r * x));
+    const float M20 = s0 * (2.f * (x * z - r * y)), M21 = s1 * (2.f * (y * z + r * x)), M22 = s2 * (1.f - 2.f * (x * x + y * y));
+    // Sigma[c][r] = M[r][0]*M[c][0] + M[r][1]*M[c][1] + M[r][2]*M[c][2]
+    c[0] = M00 * M00 + M01 * M01 + M02 * M02;
+    c[1] = M10 * M00 + M11 * M01 + M12 * M02;
+    c[2] = M20 * M00 + M21 * M01 + M22 * M02;
+    c[3] = M10 * M10 + M11 * M11 + M12 * M12;
+    c[4] = M20 * M10 + M21 * M11 + M22 * M12;
+    c[5] = M20 * M20 + M21 * M21 + M22 * M22;
 }
 
 struct SplitState {
@@ -219,10 +329,10 @@ struct FwdParams {
 };
 
 // kernels / stages (each launches on `stream`, returns hipGetLastError())
-hipError_t launch_preprocess(const FwdParams& p, const ShTone& tone, const GeometryState& g, int* radii_out, bool geom_only, hipStream_t stream);
+hipError_t launch_preprocess(const FwdParams& p, const ShTone& tone, const GeometryState& g, int* radii_out, bool geom_only, bool row, hipStream_t stream);
 // the colour half of a split frame (preprocess.hip: GEOM_ONLY): far = false the near Gaussians, far = true the others if some tile asked for them
 struct SplitState;
-hipError_t launch_sh_colour(const FwdParams& p, const GeometryState& g, const SplitState* split, bool far, hipStream_t stream);
+hipError_t launch_sh_colour(const FwdParams& p, const GeometryState& g, const SplitState* split, bool far, bool row, hipStream_t stream);
 hipError_t launch_mark_visible(int P, const float* means3D, const float* viewmatrix, unsigned char* present, hipStream_t stream);
 hipError_t launch_recolor(int P, const GeometryState& src, const GeometryState& dst, const float* colors, int* radii_out, hipStream_t stream);
 hipError_t run_scan(const GeometryState& g, int P, hipStream_t stream);
@@ -345,7 +455,8 @@ struct BwdParams {
     const float* scales;
     float scale_modifier;
     const float* rotations;
-    const float* cov3D;  // precomputed or geometry-state copy
+    const float* cov3D;  // precomputed or geometry-state copy; null with bwd_row and scales: recomputed in registers
+    const float* bwd_row = nullptr;   // the frame's backward rows (GeometryState::bwd_row) when the forward call left them: plain SH colours only
     const float* viewmatrix;
     const float* projmatrix;
     const float* campos;

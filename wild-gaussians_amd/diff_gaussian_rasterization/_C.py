@@ -80,7 +80,7 @@ _lib.wg_forward_status.restype = _i
 _lib.wg_forward_status.argtypes = [_vp, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]
 _lib.wg_mark_visible.restype = _i
 _lib.wg_mark_visible.argtypes = [_i, _vp, _vp, _vp, _vp, _vp]
-for _name in ("wg_geometry_buffer_size", "wg_binning_buffer_size"):
+for _name in ("wg_geometry_buffer_size", "wg_geometry_buffer_size_rows", "wg_binning_buffer_size"):
     getattr(_lib, _name).restype = C.c_size_t
     getattr(_lib, _name).argtypes = [_i]
 _lib.wg_image_buffer_size.restype = C.c_size_t
@@ -110,6 +110,8 @@ class _ImageView(C.Structure):
 
 _lib.wg_view_geometry.restype = _i
 _lib.wg_view_geometry.argtypes = [_vp, _i, C.POINTER(_GeometryView)]
+_lib.wg_view_backward_rows.restype = _i
+_lib.wg_view_backward_rows.argtypes = [_vp, _i, C.c_size_t, C.POINTER(_vp)]
 _lib.wg_view_binning.restype = _i
 _lib.wg_view_binning.argtypes = [_vp, _i, C.POINTER(_BinningView)]
 _lib.wg_view_image.restype = _i
@@ -468,7 +470,8 @@ def _forward_args(geom, binning, img, P, degree, M, H, W, background, means3D, s
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                         projmatrix, tan_fovx, tan_fovy, kernel_size, subpixel_offset, image_height, image_width, sh, degree,
-                        campos, prefiltered, debug, sh_tone=None, binning_capacity=None, colors2=None, filter_3D=None, sh_second=None, options=None):
+                        campos, prefiltered, debug, sh_tone=None, binning_capacity=None, colors2=None, filter_3D=None, sh_second=None, options=None,
+                        forward_only=False):
     """The reference's `rasterize_gaussians` (rasterize_points.h:18-40) plus, by keyword, everything beyond it (include/wg_rasterizer.h:
     the optional blocks of wg_rasterize_forward_ex):
     sh_tone: (mul [P,3] | None, offset [P,3] | None, pre_clamp_max | None, post_clamp_max | None) on the SH coefficients (wg_sh_tone).
@@ -478,7 +481,8 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     filter_3D: opacity / scales / rotations are the caller's RAW parameters, get_gaussians() (method.py:1060-1086) runs in-kernel.
     binning_capacity: an int = no host rendezvous at all (capturable in a hipGraph); `rendered` is then the capacity, and
       forward_status(imgBuffer, H, W) tells the real count and whether the frame fit.
-    options: per-call options (see resolve_call_options)."""
+    options: per-call options (see resolve_call_options).
+    forward_only: the caller expects no backward call for this frame (wg_forward_args::forward_only; a hint: results are the same either way)."""
     opts = resolve_call_options(options)
     H, W = int(image_height), int(image_width)
     key = None
@@ -523,11 +527,11 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     if _torch_ext is not None:   # the compiled binding (csrc/torch_binding.cpp): the whole surface but the recolouring above
         res = _torch_ext.rasterize_gaussians_ex(background, means3D, colors, opacity, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix,
                                                 projmatrix, float(tan_fovx), float(tan_fovy), float(kernel_size), subpixel_offset, H, W, sh, int(degree),
-                                                campos, bool(prefiltered), bool(debug), sh_tone, binning_capacity, colors2, filter_3D, sh_second, opts)
+                                                campos, bool(prefiltered), bool(debug), sh_tone, binning_capacity, colors2, filter_3D, sh_second, opts, bool(forward_only))
     else:
         res = _forward_ctypes(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
                               tan_fovy, kernel_size, subpixel_offset, H, W, sh, degree, campos, prefiltered, debug, sh_tone, binning_capacity, colors2,
-                              filter_3D, sh_second, opts, device, P)
+                              filter_3D, sh_second, opts, device, P, forward_only)
     if binning_capacity is not None:
         _reuse.last_fixed = (res[5], H, W)
     # (never a parent whose verdict is not in yet: see "Geometry reuse" above)
@@ -539,7 +543,7 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 
 def _forward_ctypes(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                     kernel_size, subpixel_offset, H, W, sh, degree, campos, prefiltered, debug, sh_tone, binning_capacity, colors2, filter_3D, sh_second,
-                    opts, device, P):
+                    opts, device, P, forward_only=False):
     """The checked forward call through ctypes -> the reference's six, + the second image with colors2 / sh_second."""
     geom, binning, img = _Scratch(device), _Scratch(device), _Scratch(device)
     two = colors2 is not None or sh_second is not None
@@ -561,6 +565,7 @@ def _forward_ctypes(background, means3D, colors, opacity, scales, rotations, sca
                           second=_second_block(device, colors2=colors2, out_color2=out_color2) if two else None,
                           raw=None if filter_3D is None else _raw_block(device, filter_3D))
     a.binning_capacity = int(binning_capacity or 0)
+    a.forward_only = int(bool(forward_only))
     try:
         with torch.cuda.device(device):
             rendered = _lib.wg_rasterize_forward_ex(C.byref(a))
@@ -744,9 +749,11 @@ def _from_ptr(ptr, shape, dtype, owner):
 def view_geometry(geomBuffer, P):
     v = _GeometryView()
     _check(_lib.wg_view_geometry(geomBuffer.data_ptr(), int(P), C.byref(v)), "wg_view_geometry")
+    rows = _vp()   # (None for a frame that left no backward rows: its buffer does not hold the array)
+    _check(_lib.wg_view_backward_rows(geomBuffer.data_ptr(), int(P), geomBuffer.numel(), C.byref(rows)), "wg_view_backward_rows")
     return dict(depths=_from_ptr(v.depths, (P,), torch.float32, geomBuffer), radii=_from_ptr(v.radii, (P,), torch.int32, geomBuffer),
                 splats=_from_ptr(v.splats, (P, 12), torch.float32, geomBuffer), cov3D=_from_ptr(v.cov3D, (P, 6), torch.float32, geomBuffer),
-                clamped=_from_ptr(v.clamped, (P,), torch.uint8, geomBuffer),
+                clamped=_from_ptr(v.clamped, (P,), torch.uint8, geomBuffer), bwd_row=_from_ptr(rows.value, (P, 10), torch.float32, geomBuffer) if rows.value else None,
                 tiles_touched=_from_ptr(v.tiles_touched, (P,), torch.int32, geomBuffer),
                 point_offsets=_from_ptr(v.point_offsets, (P,), torch.int32, geomBuffer))
 

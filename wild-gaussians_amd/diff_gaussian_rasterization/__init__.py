@@ -78,7 +78,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                 sh_mul=None, sh_offset=None, sh_pre_clamp_max=None, sh_post_clamp_max=None, binning_capacity=None, colors_precomp2=None,
                 filter_3D=None, sh_second=False, sh_mul2=None, sh_offset2=None, sh_pre_clamp_max2=None, sh_post_clamp_max2=None, call_options=None,
-                colour_gradients_only=None):
+                colour_gradients_only=None, grad_mode=True):
         rs = raster_settings
         native_args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                        rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.kernel_size, rs.subpixel_offset,
@@ -88,6 +88,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         # per-call options: resolved ONCE here (keyword > the calling thread's defaults) and carried to the backward call on ctx
         ctx.call_options = _C.resolve_call_options(call_options)
         extra = dict(options=ctx.call_options)
+        # nothing takes a gradient (grad mode was off at the call -- it always is in here, so the caller passes it --, or no input requires
+        # one): no backward call will follow, the frame leaves nothing for one (wg_forward_args::forward_only)
+        extra["forward_only"] = not (grad_mode and any(ctx.needs_input_grad))
         # the colour-only backward pass (wg_backward_args::colour_gradients_only): resolved ONCE here too (keyword > the calling thread's default);
         # what it cannot serve is refused now, not in the middle of a backward pass
         ctx.colour_only = _C.resolve_colour_gradients_only(colour_gradients_only)
@@ -160,7 +163,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         extra = dict(options=ctx.call_options, colour_gradients_only=ctx.colour_only)   # the frame's forward call's
         if ctx.colour_only:   # dL_dcolors and nothing else: the geometry inputs' .grad stay as they were
             g_colors = _call_native(lambda *a: _C.rasterize_gaussians_backward(*a, **extra), native_args, rs.debug, "snapshot_bw.dump", "backward")[1]
-            return (None, None, None, g_colors) + (None,) * 19
+            return (None, None, None, g_colors) + (None,) * 20
         if ctx.sh_tone is not None:
             extra["sh_tone"] = ctx.sh_tone
         if ctx.raw:
@@ -184,7 +187,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             g_mul, g_offset = shaped(res[8], ctx.sh_tone[0]), shaped(res[9], ctx.sh_tone[1])
         # order of forward()'s inputs; None for raster_settings, the clamp constants and the options
         return (g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3Ds, None, g_mul, g_offset, None, None, None, g_colors2, None,
-                None, g_mul2, g_offset2, None, None, None, None)
+                None, g_mul2, g_offset2, None, None, None, None, None)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
@@ -194,7 +197,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                      raster_settings, sh_mul, sh_offset, sh_pre_clamp_max, sh_post_clamp_max, binning_capacity, colors_precomp2,
                                      filter_3D, sh_second, sh_mul2, sh_offset2, sh_pre_clamp_max2, sh_post_clamp_max2, call_options,
-                                     colour_gradients_only)
+                                     colour_gradients_only, torch.is_grad_enabled())
 
 
 class GaussianRasterizer(nn.Module):

@@ -34,7 +34,8 @@ class _ForwardArgs(C.Structure):  # wg_forward_args
                 [(n, _vp) for n in ("background", "means3D", "shs", "colors_precomp", "opacities", "scales", "rotations", "cov3D_precomp", "viewmatrix",
                                     "projmatrix", "cam_pos", "subpixel_offset", "out_color", "radii", "stream")] +
                 [("tone", C.POINTER(_ShTone)), ("tone2", C.POINTER(_ShTone)), ("sh_second", _i), ("second", C.POINTER(_SecondImage)),
-                 ("raw", C.POINTER(_RawGaussians)), ("recolor", C.POINTER(_RecolorParent)), ("binning_capacity", _i), ("options", C.POINTER(_CallOptions))])
+                 ("raw", C.POINTER(_RawGaussians)), ("recolor", C.POINTER(_RecolorParent)), ("binning_capacity", _i), ("forward_only", _i),   # (forward_only: the four bytes that were padding; sizeof stays 288)
+                 ("options", C.POINTER(_CallOptions))])
 
 
 class _BackwardArgs(C.Structure):  # wg_backward_args
