@@ -67,6 +67,15 @@ A switch of its own, on a TRAINER object instead of the module, and off unless c
                         8-bit frames live on the device as uint8 and every access is one HIP kernel that writes the float32 tensor
                         `.to(device)` would deliver, bit for bit; `uncertainty_model._images_cache` (method.py:262-264) ->
                         wg_frame_store.FeatureCache, whose values stay on the device.  The caller's `.to(device)` lines become no-ops
+
+And one on the EVALUATION module (`wildgaussians.evaluation`, not `method`), off unless called (logged metrics move within rounding):
+
+    undo = wg_integration.fuse_evaluation_metrics(evaluation)         # before the evaluation protocol object is built
+  evaluation metrics    `evaluation.compute_metrics` (evaluation.py:331-352) -> wg_fused_metrics.compute_metrics: MSE, MAE and dm_pix's SSIM of
+                        every image pair in one HIP kernel and a finishing launch (float32 values and products, float64 filtering, as NumPy
+                        computes them), three doubles read back; LPIPS stays the module's own `lpips` / `lpips_vgg`.  Calls it does not cover
+                        (anything but two uint8 / float32 NumPy arrays [..., H, W, C] with C <= 4 and H, W >= 11, no HIP device) go to the
+                        original function
 """
 from __future__ import annotations
 
@@ -302,4 +311,47 @@ def keep_training_frames_on_device(trainer, device=None, max_device_bytes=None, 
     undo.stats = lambda: {"budget_bytes": budget.total, "used_bytes": budget.used, "images": images.stats(),
                           "masks": masks.stats() if masks is not None else None,
                           "features": undo.features.stats() if undo.features is not None else None}
+    return undo
+
+
+def fuse_evaluation_metrics(evaluation_module):
+    """Swap `evaluation_module.compute_metrics` (the reference's wildgaussians/evaluation.py:331-352) for a wrapper over
+    wg_fused_metrics.compute_metrics.  -> a function that puts the original back.  Off unless called.
+
+    The wrapper takes the fused path when both arguments are NumPy arrays of dtype uint8 or float32 with the same leading shape
+    [..., H, W], at least three dimensions, at most 4 channels after the reference's channel slice (`pred[..., :gt.shape[-1]]`) and
+    H, W >= 11, and a HIP device is present.  Every other call goes to the caller's original function with the caller's arguments.
+    `lpips` and `lpips_vgg` are looked up in `evaluation_module` at call time: the caller's networks are used unchanged.
+
+    Limits.  A protocol object that captured `compute_metrics` before the swap keeps the original: `NerfWEvaluationProtocol.__init__` stores
+    it as an attribute, so call this first.  `render()` and `image_to_srgb` are not touched: linear colour space, background blending and
+    alpha stay the caller's.  Logged values move: SSIM by about 1e-10 and less, MSE / MAE / PSNR by the difference between NumPy's float32
+    mean and a float64 sum of the same float32 terms (about 1e-7 relative), which is why this is off unless called."""
+    import numpy as np
+    original = evaluation_module.compute_metrics
+
+    def covered(pred, gt):
+        if not (isinstance(pred, np.ndarray) and isinstance(gt, np.ndarray)):
+            return False
+        if pred.dtype not in (np.uint8, np.float32) or gt.dtype not in (np.uint8, np.float32):
+            return False
+        if gt.ndim < 3 or pred.ndim != gt.ndim or pred.shape[:-1] != gt.shape[:-1] or pred.shape[-1] < gt.shape[-1]:
+            return False
+        if not 1 <= gt.shape[-1] <= 4 or gt.shape[-3] < 11 or gt.shape[-2] < 11 or any(n == 0 for n in gt.shape):
+            return False
+        return torch.cuda.is_available()
+
+    def compute_metrics(*args, **kwargs):
+        if len(args) != 2 or set(kwargs) - {"reduce", "run_lpips_vgg"} or not covered(*args):
+            return original(*args, **kwargs)
+        import wg_fused_metrics
+        return wg_fused_metrics.compute_metrics(*args, **kwargs, lpips=evaluation_module.lpips,
+                                                lpips_vgg=getattr(evaluation_module, "lpips_vgg", None))
+
+    compute_metrics.__wrapped__ = original
+    evaluation_module.compute_metrics = compute_metrics
+
+    def undo():
+        if evaluation_module.compute_metrics is compute_metrics:
+            evaluation_module.compute_metrics = original
     return undo
