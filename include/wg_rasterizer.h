@@ -77,7 +77,9 @@ int wg_rasterize_forward(wg_alloc_fn geometry_alloc, void* geometry_user, wg_all
 /* Rasterizer::backward (rasterizer.h:61-88, rasterizer_impl.cu:344-443).  The reference wants all nine gradient outputs zero-filled
  * (rasterize_points.cu:157-165); here (options->grad_record = 1, the default) all nine are fully OVERWRITTEN (zeros for culled
  * Gaussians) -- a caller following the reference's protocol gets the same values -- and dL_dconic (an intermediate of the
- * reference) and, with SH colours, dL_dcolor may be NULL.  dL_dconic: float[P*4], 16-byte aligned ([0],[1],[3] used);
+ * reference) and, with SH colours, dL_dcolor may be NULL.  dL_dcov3D may be NULL whenever cov3D_precomp is (with scales and rotations
+ * it is an intermediate too: its chain rule is applied into dL_dscale / dL_drot either way, only the store is left out) -- with or
+ * without the record.  dL_dconic: float[P*4], 16-byte aligned ([0],[1],[3] used);
  * dL_dmean2D: float[P*3] (x, y NDC-scaled, z = abs-gradient, backward.cu:590-595); dL_dsh may be NULL when M == 0. */
 int wg_rasterize_backward(int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
                           const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,

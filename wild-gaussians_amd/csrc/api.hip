@@ -650,22 +650,41 @@ void order_tables_release() {
 }
 
 // row / geom: whether the frame's forward call left backward rows (wg_common.h: BWD_ROW_FLOATS), and in which geometry buffer
-struct FrameMode { const void* image; int exact; int row; const void* geom; };
+// clean_floats: the floats of the gradient record (inside geom) that the frame's forward render launch zeroed for the backward call, 0 = none
+struct FrameMode { const void* image; int exact; int row; const void* geom; size_t clean_floats; };
 // read-only counters of the process (wg_get_option): forward calls that left backward rows, backward calls that ran on them
 std::atomic<uint64_t> g_row_frames{0}, g_row_backwards{0};
+// ... forward calls whose render launch cleared the gradient record, backward calls that found it clean and cleared nothing
+std::atomic<uint64_t> g_clean_frames{0}, g_clean_backwards{0};
 std::mutex g_mode_mu;
 FrameMode g_modes[64];
 unsigned g_mode_head = 0;
 const void* image_key(const char* image_buffer) {
     return reinterpret_cast<const void*>((reinterpret_cast<uintptr_t>(image_buffer) + wg::ALIGN - 1) & ~(uintptr_t)(wg::ALIGN - 1));
 }
-void remember_mode(const char* image_buffer, int exact, int row, const char* geom_buffer) {
+void remember_mode(const char* image_buffer, int exact, int row, const char* geom_buffer, size_t clean_floats) {
     const void* k = image_key(image_buffer);
     const void* gk = image_key(geom_buffer);
     std::lock_guard<std::mutex> l(g_mode_mu);
     for (auto& m : g_modes)
-        if (m.image == k) { m.exact = exact; m.row = row; m.geom = gk; return; }
-    g_modes[g_mode_head++ % 64] = {k, exact, row, gk};
+        if (m.image == k) { m.exact = exact; m.row = row; m.geom = gk; m.clean_floats = clean_floats; return; }
+    g_modes[g_mode_head++ % 64] = {k, exact, row, gk, clean_floats};
+}
+// Whether the frame's forward render launch left the first `floats` floats of this geometry buffer's gradient record zeroed and no backward
+// call has accumulated into them since: the mark is taken by the one call that finds it, a second backward over the same frame (a retained
+// graph) clears for itself.  A call over another geometry buffer (a recoloured child of the frame) leaves the mark where it is.
+bool take_record_clean(const char* image_buffer, const char* geom_buffer, size_t floats) {
+    const void* k = image_key(image_buffer);
+    const void* gk = image_key(geom_buffer);
+    std::lock_guard<std::mutex> l(g_mode_mu);
+    for (auto& m : g_modes)
+        if (m.image == k) {
+            if (m.geom != gk || m.clean_floats == 0) return false;
+            const bool covers = m.clean_floats >= floats;
+            m.clean_floats = 0;
+            return covers;
+        }
+    return false;
 }
 // whether the frame of this image buffer left backward rows in this geometry buffer (a frame that is not remembered did not, as far as its
 // backward call can tell: it takes the kernel that needs none)
@@ -816,6 +835,7 @@ struct ForwardFrame {
     uint32_t order_slots = 0, near_per_tile = 0;
     bool try_split = false, lazy_colour = false;
     bool row = false;   // the frame leaves backward rows: plain SH colours and a backward call expected (wg_forward_args::forward_only = 0)
+    size_t clear_floats = 0;   // the gradient record's floats the main render launch zeroes for the frame's backward call (0: it clears for itself)
     Mailbox* mbox = nullptr;
     // ---- what depends on the instance count, as functions of it (used by the speculative and by the classic flow alike) ----
     // Longest per-tile list decides the binning path: full register sort of every tile, lazy front sort when lists are long,
@@ -940,7 +960,7 @@ int ForwardFrame::enqueue_tail(const wg::BinningState& bin, uint32_t R, uint32_t
     if (lazy) WG_STAGE(WG_STAGE_SORT, wg::launch_tile_sort_lazy(img, bin, geom, tiles, code_bits, opt.lazy, try_split, guard, stream), "tile_sort_lazy");
     else WG_STAGE(WG_STAGE_SORT, wg::launch_tile_sort(img, bin, geom, tiles, longest, guard, stream), "tile_sort");
     WG_STAGE(WG_STAGE_RENDER_FORWARD,
-             wg::launch_render_forward(width, height, gx, gy, img, bin, geom, a.subpixel_offset, a.background, a.out_color, out_color2, lazy, opt.exact_compositing != 0, guard, order_table, order_slots, ORDER_STRIDE, stream),
+             wg::launch_render_forward(width, height, gx, gy, img, bin, geom, a.subpixel_offset, a.background, a.out_color, out_color2, lazy, opt.exact_compositing != 0, guard, clear_floats ? geom.grad_rec : nullptr, clear_floats, order_table, order_slots, ORDER_STRIDE, stream),
              "render_forward");
     if (lazy) {
         WG_STAGE(WG_STAGE_RENDER_FIXUP,
@@ -992,7 +1012,7 @@ int ForwardFrame::global_sort_tail(const wg::BinningState& bin, int num_rendered
         if (huge_frame) WG_STAGE(WG_STAGE_TILE_RANGES, wg::launch_tile_ranges(num_rendered, bin, img, tiles, stream), "tile_ranges");
     }
     WG_STAGE(WG_STAGE_RENDER_FORWARD,
-             wg::launch_render_forward(width, height, gx, gy, img, bin, geom, a.subpixel_offset, a.background, a.out_color, out_color2, false, opt.exact_compositing != 0, nullptr, order_table, order_slots, ORDER_STRIDE, stream),
+             wg::launch_render_forward(width, height, gx, gy, img, bin, geom, a.subpixel_offset, a.background, a.out_color, out_color2, false, opt.exact_compositing != 0, nullptr, clear_floats ? geom.grad_rec : nullptr, clear_floats, order_table, order_slots, ORDER_STRIDE, stream),
              "render_forward");
     return num_rendered;
 }
@@ -1013,8 +1033,15 @@ static int forward_impl(const wg_forward_args& a) {
     char* geom_chunk = a.geometry_alloc(required_bytes([&](char*& c) { wg::GeometryState::fromChunk(c, (size_t)P, band_lists, rows); }), a.geometry_user);
     char* img_chunk = a.image_alloc(wg_image_buffer_size(a.width, a.height), a.image_user);
     if (!geom_chunk || !img_chunk) return WG_ERR_ALLOC;
-    remember_mode(img_chunk, opt.exact_compositing ? 1 : 0, f.row ? 1 : 0, geom_chunk);
+    // The gradient record of a frame that expects an atomic-mode backward call is zeroed by the frame's main render launch, whose waves leave
+    // HBM nearly idle, instead of by the launch in front of the backward render kernel (render_fwd.hip: fwd_clear_record).  Every way through
+    // this function that returns a frame runs that launch once at least, and its waves clear whatever the speculation's verdict says.
+    // Deterministic mode writes every record in full and clears nothing.
+    f.clear_floats = (P > 0 && a.forward_only == 0 && opt.grad_record && !opt.deterministic_backward)
+                         ? (size_t)P * (wg::GRAD_REC_FLOATS + (a.second != nullptr ? 1 : 0)) : 0;
+    remember_mode(img_chunk, opt.exact_compositing ? 1 : 0, f.row ? 1 : 0, geom_chunk, f.clear_floats);
     if (f.row) g_row_frames.fetch_add(1, std::memory_order_relaxed);
+    if (f.clear_floats) g_clean_frames.fetch_add(1, std::memory_order_relaxed);
     f.geom = wg::GeometryState::fromChunk(geom_chunk, (size_t)P, band_lists, rows);
     f.img = wg::ImageState::fromChunk(img_chunk, (size_t)a.width * a.height, (size_t)tiles);
     f.fp = forward_params(a, opt, f.gx, f.gy);
@@ -1179,7 +1206,10 @@ static int backward_impl(const wg_backward_args& a) {
     if (P < 0 || R < 0 || width <= 0 || height <= 0) return WG_ERR_INVALID_ARGUMENT;
     if (P == 0) return WG_OK;
     if (!geom_buffer || !binning_buffer || !image_buffer || !dL_dpix || !background) return WG_ERR_INVALID_ARGUMENT;
-    if (!dL_dmean2D || !dL_dopacity || !dL_dmean3D || !dL_dcov3D) return WG_ERR_INVALID_ARGUMENT;
+    if (!dL_dmean2D || !dL_dopacity || !dL_dmean3D) return WG_ERR_INVALID_ARGUMENT;
+    // dL_dcov3D is an intermediate when the covariance comes from scales and rotations (its chain rule is applied into dL_dscale / dL_drot):
+    // only a caller that handed over cov3D_precomp must take it
+    if (!dL_dcov3D && cov3D_precomp != nullptr) return WG_ERR_INVALID_ARGUMENT;
     // dL_dconic (always an intermediate) and, with SH colours, dL_dcolor (the gradient of the evaluated RGB, an intermediate there)
     // may be NULL with the gradient record: nobody reads them.  Without the record they are accumulation targets.
     if (!g_grad_record && !opt.deterministic_backward && (!dL_dconic || !dL_dcolor)) return WG_ERR_INVALID_ARGUMENT;
@@ -1233,7 +1263,18 @@ static int backward_impl(const wg_backward_args& a) {
     }
     // the gradient records are cleared by the launch that orders the tiles (one launch instead of a fill kernel + the ordering);
     // the deterministic mode's ordered sum writes every record in full and needs no clearing
-    const bool clear_records = record && !det;
+    // ... and neither does a record that the frame's forward render launch left zeroed (forward_impl: clear_floats) and that no backward call
+    // has touched since.  The mark is consumed by whichever full backward call of the frame comes first, so a second one (a retained graph)
+    // clears as ever; so does a call whose stream is being captured -- a replay would accumulate onto what the replay before it left.
+    const size_t record_floats = (size_t)P * (wg::GRAD_REC_FLOATS + (dual ? 1 : 0));
+    bool record_clean = take_record_clean(a.image_buffer, a.geom_buffer, record_floats) && record && !det && R > 0;
+    if (record_clean) {
+        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(stream, &capturing) != hipSuccess) { (void)hipGetLastError(); record_clean = false; }
+        else if (capturing != hipStreamCaptureStatusNone) record_clean = false;
+    }
+    if (record_clean) g_clean_backwards.fetch_add(1, std::memory_order_relaxed);
+    const bool clear_records = record && !det && !record_clean;
     if (clear_records && R <= 0) {
         StageScope scope_(WG_STAGE_RENDER_BACKWARD, stream);
         hipError_t e = hipMemsetAsync(geom.grad_rec, 0, (size_t)P * (wg::GRAD_REC_FLOATS + (dual ? 1 : 0)) * sizeof(float), stream);
@@ -1468,6 +1509,9 @@ int wg_get_option(const char* name) {
     // read-only counters of the process: forward calls that left backward rows / backward calls that took the row kernel
     if (std::strcmp(name, "backward_row_frames") == 0) return (int)std::min<uint64_t>(g_row_frames.load(std::memory_order_relaxed), 0x7fffffffu);
     if (std::strcmp(name, "backward_row_calls") == 0) return (int)std::min<uint64_t>(g_row_backwards.load(std::memory_order_relaxed), 0x7fffffffu);
+    // ... forward calls whose render launch zeroed the gradient record / backward calls that found it clean and cleared nothing
+    if (std::strcmp(name, "record_clean_frames") == 0) return (int)std::min<uint64_t>(g_clean_frames.load(std::memory_order_relaxed), 0x7fffffffu);
+    if (std::strcmp(name, "record_clean_calls") == 0) return (int)std::min<uint64_t>(g_clean_backwards.load(std::memory_order_relaxed), 0x7fffffffu);
     const OptionRow* r = find_option(name);
     return r ? r->get(options_snapshot()) : -1;
 }

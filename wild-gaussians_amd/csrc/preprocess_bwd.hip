@@ -319,8 +319,10 @@ __global__ void __launch_bounds__(64) preprocess_backward_kernel(
 
     // ---- the outputs that do not depend on the SH block ----
     if (in) {
-        float* o = dL_dcov3D + 6 * (size_t)idx;
-        o[0] = dcov[0]; o[1] = dcov[1]; o[2] = dcov[2]; o[3] = dcov[3]; o[4] = dcov[4]; o[5] = dcov[5];
+        if (dL_dcov3D) {   // (NULL: covariance from scales and rotations, whose gradients carry it -- nobody reads the intermediate)
+            float* o = dL_dcov3D + 6 * (size_t)idx;
+            o[0] = dcov[0]; o[1] = dcov[1]; o[2] = dcov[2]; o[3] = dcov[3]; o[4] = dcov[4]; o[5] = dcov[5];
+        }
         if (RECORD) {
             dL_dopacity[idx] = write_dLdo ? dLdo_out : dLdo_in;
             dL_dmean2D[3 * idx] = g2x; dL_dmean2D[3 * idx + 1] = g2y; dL_dmean2D[3 * idx + 2] = g2abs;

@@ -324,6 +324,17 @@ __device__ uint32_t fwd_store(const FwdTile& st, bool complete, int W, int H, in
 #if WG_PROBE
 __device__ unsigned long long g_fwd_probe[4 * 65536];
 #endif
+// The frame's gradient record (api.hip: ForwardFrame::clear_floats), zeroed for its backward call: wave b takes float4s
+// [b * rec_per_wave, (b + 1) * rec_per_wave) below rec_vec4, 16-byte stores.  The wave's LAST act: nothing of the walk is live any more (no
+// register, no scratch more), nothing waits for the stores, and the waves of a launch end spread over its whole duration, so the 48 B per
+// Gaussian trickle into an HBM the walk leaves nearly idle.  (As the wave's FIRST act all ~8 k resident waves store at once and every
+// wave's first loads queue behind the burst: K8 +5.5 us, EXPERIMENTS.md R9.1.)
+__device__ __forceinline__ void fwd_clear_record(float4* __restrict__ rec_clear, size_t rec_vec4, uint32_t rec_per_wave) {
+    if (!rec_clear) return;
+    const size_t begin = (size_t)blockIdx.x * rec_per_wave;
+    const size_t stop = begin + rec_per_wave < rec_vec4 ? begin + rec_per_wave : rec_vec4;
+    for (size_t i = begin + threadIdx.x; i < stop; i += 64) rec_clear[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
 template <bool EXACT, bool DUAL>
 __device__ __forceinline__ void render_forward_body(
     float4* lds, int W, int H, int gx, int tiles, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
@@ -332,8 +343,11 @@ __device__ __forceinline__ void render_forward_body(
     float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, uint32_t* tile_last,
     float* __restrict__ out_color, const BinStats* __restrict__ guard, int replay, float* __restrict__ accum, float* __restrict__ out_color2,
     const uint32_t* __restrict__ order, const uint32_t* __restrict__ order_key, uint32_t* __restrict__ order_table, uint32_t order_slots,
-    uint32_t order_stride) {
-    if (guard && guard->spec_fail) return;  // speculative forward (api.hip): the frame did not fit what was enqueued; the host re-issues
+    uint32_t order_stride, float4* __restrict__ rec_clear, size_t rec_vec4, uint32_t rec_per_wave) {
+    if (guard && guard->spec_fail) {  // speculative forward (api.hip): the frame did not fit what was enqueued; the host re-issues
+        fwd_clear_record(rec_clear, rec_vec4, rec_per_wave);   // (a fixed-capacity or deferred frame is not re-issued: its backward pass accumulates nothing onto a clean record)
+        return;
+    }
 #if WG_PROBE
     const unsigned long long probe_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -356,6 +370,7 @@ __device__ __forceinline__ void render_forward_body(
         order_table[2 * (size_t)order_slots + (size_t)slot * order_stride + tile] = walked + 1u;   // (+1: staging and stores cost something for an empty tile too)
         if (blockIdx.x == 0) { order_table[2 * (size_t)slot] = order_key[1]; order_table[2 * (size_t)slot + 1] = order_key[2]; }
     }
+    fwd_clear_record(rec_clear, rec_vec4, rec_per_wave);
 #if WG_PROBE
     if (lane == 0 && blockIdx.x < 65536) {
         g_fwd_probe[4 * blockIdx.x] = probe_t0;
@@ -375,10 +390,11 @@ __global__ void __launch_bounds__(64) WG_FWD_OCC render_forward_kernel(
     const uint32_t* seg_end, uint32_t* __restrict__ tile_state,
     float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, uint32_t* tile_last,
     float* __restrict__ out_color, const BinStats* __restrict__ guard, int replay, float* __restrict__ accum,
-    const uint32_t* __restrict__ order, const uint32_t* __restrict__ order_key, uint32_t* __restrict__ order_table, uint32_t order_slots, uint32_t order_stride) {
+    const uint32_t* __restrict__ order, const uint32_t* __restrict__ order_key, uint32_t* __restrict__ order_table, uint32_t order_slots, uint32_t order_stride,
+    float4* __restrict__ rec_clear, size_t rec_vec4, uint32_t rec_per_wave) {
     __shared__ float4 lds[BATCH * 3];
     render_forward_body<EXACT, false>(lds, W, H, gx, tiles, ranges, point_list, splats, subpixel_offset, bg, seg_end, tile_state, final_T, n_contrib,
-                                      tile_last, out_color, guard, replay, accum, nullptr, order, order_key, order_table, order_slots, order_stride);
+                                      tile_last, out_color, guard, replay, accum, nullptr, order, order_key, order_table, order_slots, order_stride, rec_clear, rec_vec4, rec_per_wave);
 }
 
 // the two-colour walk keeps twelve more sums per lane: its register allocation is left to the compiler (no occupancy pin)
@@ -397,30 +413,37 @@ __global__ void __launch_bounds__(64) WG_FWD_DUAL_OCC render_forward_dual_kernel
     const uint32_t* seg_end, uint32_t* __restrict__ tile_state,
     float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, uint32_t* tile_last,
     float* __restrict__ out_color, const BinStats* __restrict__ guard, float* __restrict__ accum, float* __restrict__ out_color2,
-    const uint32_t* __restrict__ order, const uint32_t* __restrict__ order_key, uint32_t* __restrict__ order_table, uint32_t order_slots, uint32_t order_stride) {
+    const uint32_t* __restrict__ order, const uint32_t* __restrict__ order_key, uint32_t* __restrict__ order_table, uint32_t order_slots, uint32_t order_stride,
+    float4* __restrict__ rec_clear, size_t rec_vec4, uint32_t rec_per_wave) {
     __shared__ float4 lds[BATCH * 3];
     render_forward_body<EXACT, true>(lds, W, H, gx, tiles, ranges, point_list, splats, subpixel_offset, bg, seg_end, tile_state, final_T, n_contrib,
-                                     tile_last, out_color, guard, 0, accum, out_color2, order, order_key, order_table, order_slots, order_stride);
+                                     tile_last, out_color, guard, 0, accum, out_color2, order, order_key, order_table, order_slots, order_stride, rec_clear, rec_vec4, rec_per_wave);
 }
 
 hipError_t launch_render_forward(int W, int H, int gx, int gy, const ImageState& img, const BinningState& b,
                                  const GeometryState& g, const float* subpixel_offset, const float* background,
-                                 float* out_color, float* out_color2, bool lazy, bool exact, const BinStats* guard, uint32_t* order_table,
-                                 uint32_t order_slots, uint32_t order_stride, hipStream_t stream) {
+                                 float* out_color, float* out_color2, bool lazy, bool exact, const BinStats* guard, float* record_clear,
+                                 size_t record_floats, uint32_t* order_table, uint32_t order_slots, uint32_t order_stride, hipStream_t stream) {
     const int tiles = gx * gy;
     if (tiles <= 0) return hipSuccess;
+    // the record's float4s (rounded UP, as launch_tile_order rounds them), dealt to the launch's waves in equal contiguous shares
+    float4* const rec_clear = record_floats ? reinterpret_cast<float4*>(record_clear) : nullptr;
+    const size_t rec_vec4 = rec_clear ? (record_floats + 3) / 4 : 0;
+    const size_t share = (rec_vec4 + (size_t)tiles - 1) / (size_t)tiles;
+    if (share > 0xffffffffu) return hipErrorInvalidValue;
+    const uint32_t rec_per_wave = (uint32_t)share;
     const uint32_t* order = order_table ? img.order_fwd : (const uint32_t*)nullptr;
     const uint32_t* okey = order_table ? img.order_key : (const uint32_t*)nullptr;
 #define WG_LAUNCH(EX)                                                                                                                       \
     hipLaunchKernelGGL(render_forward_kernel<EX>, dim3(tiles), dim3(64), 0, stream, W, H, gx, tiles, img.ranges, b.point_list, g.splats,   \
                        reinterpret_cast<const float2*>(subpixel_offset), background, lazy ? img.seg_end : (const uint32_t*)nullptr,        \
                        lazy ? img.tile_state : (uint32_t*)nullptr, img.final_T, img.n_contrib, img.tile_last, out_color, guard, 0, img.accum, \
-                       order, okey, order_table, order_slots, order_stride)
+                       order, okey, order_table, order_slots, order_stride, rec_clear, rec_vec4, rec_per_wave)
 #define WG_LAUNCH_DUAL(EX)                                                                                                                  \
     hipLaunchKernelGGL(render_forward_dual_kernel<EX>, dim3(tiles), dim3(64), 0, stream, W, H, gx, tiles, img.ranges, b.point_list, g.splats, \
                        reinterpret_cast<const float2*>(subpixel_offset), background, lazy ? img.seg_end : (const uint32_t*)nullptr,        \
                        lazy ? img.tile_state : (uint32_t*)nullptr, img.final_T, img.n_contrib, img.tile_last, out_color, guard, img.accum, out_color2, \
-                       order, okey, order_table, order_slots, order_stride)
+                       order, okey, order_table, order_slots, order_stride, rec_clear, rec_vec4, rec_per_wave)
     if (out_color2) { if (exact) WG_LAUNCH_DUAL(true); else WG_LAUNCH_DUAL(false); }
     else { if (exact) WG_LAUNCH(true); else WG_LAUNCH(false); }
 #undef WG_LAUNCH
@@ -437,7 +460,7 @@ hipError_t launch_render_forward_replay(int W, int H, int gx, int gy, const Imag
     hipLaunchKernelGGL(render_forward_kernel<EX>, dim3(tiles), dim3(64), 0, stream, W, H, gx, tiles, img.ranges, b.point_list, g.splats,   \
                        reinterpret_cast<const float2*>(subpixel_offset), background, (const uint32_t*)img.tile_last, (uint32_t*)nullptr,   \
                        img.final_T, img.n_contrib, img.tile_last, out_color, (const BinStats*)nullptr, 1, img.accum,                        \
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0u, 0u)
+                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0u, 0u, (float4*)nullptr, (size_t)0, 0u)
     if (exact) WG_LAUNCH(true); else WG_LAUNCH(false);
 #undef WG_LAUNCH
     return hipGetLastError();

@@ -208,7 +208,8 @@ struct Gradients {
 
 Gradients backward(const Scene& s, const torch::Tensor& radii, const torch::Tensor& dL_dout_color, const torch::Tensor& geomBuffer, const int R,
                    const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const py::object& sh_tone, const OptTensor& dL_dout_color2,
-                   const py::object& raw_in, const py::object& sh_second, const wg_call_options& co, const bool colour_only = false) {
+                   const py::object& raw_in, const py::object& sh_second, const wg_call_options& co, const bool colour_only = false,
+                   const bool want_colors = true, const bool want_cov3D = true) {
     const auto dev = s.means3D.device();
     const c10::DeviceGuard guard(dev);
     const int P = static_cast<int>(s.means3D.size(0));
@@ -265,9 +266,14 @@ Gradients backward(const Scene& s, const torch::Tensor& radii, const torch::Tens
     auto alloc = [&](std::initializer_list<int64_t> shape, bool written) {
         return (P != 0 && written) ? torch::empty(shape, f) : torch::zeros(shape, f);
     };
+    // want_colors / want_cov3D = false: the caller reads neither (the autograd function, for inputs that take no gradient).  Where the library
+    // treats them as intermediates -- dL_dcolor with SH colours and the record, dL_dcov3D without cov3D_precomp -- they are then neither
+    // allocated nor handed over (the per-Gaussian kernel skips the stores) and stay undefined; anywhere else they exist as ever.
+    const bool colors_out = want_colors || !record || s.sh.numel() == 0, cov3D_out = want_cov3D || s.cov3D_precomp.numel() != 0;
     Gradients g;
-    g.means3D = alloc({P, 3}, true); g.means2D = alloc({P, 3}, record); g.colors = alloc({P, 3}, record); g.opacity = alloc({P, 1}, record);
-    g.cov3D = alloc({P, 6}, true); g.sh = alloc({P, M, 3}, true); g.scales = alloc({P, 3}, have_scales); g.rotations = alloc({P, 4}, have_scales);
+    g.means3D = alloc({P, 3}, true); g.means2D = alloc({P, 3}, record); g.opacity = alloc({P, 1}, record);
+    if (colors_out) g.colors = alloc({P, 3}, record);
+    if (cov3D_out) g.cov3D = alloc({P, 6}, true); g.sh = alloc({P, M, 3}, true); g.scales = alloc({P, 3}, have_scales); g.rotations = alloc({P, 4}, have_scales);
     const torch::Tensor dL_dconic = record ? torch::Tensor() : torch::zeros({P, 2, 2}, f);
     if (dual) g.colors2 = alloc({P, 3}, true);
     if (tone.t.mul) g.mul = alloc({P, 3}, true);
@@ -287,8 +293,8 @@ Gradients backward(const Scene& s, const torch::Tensor& radii, const torch::Tens
     a.geom_buffer = bytes_of(geomBuffer); a.binning_buffer = bytes_of(binningBuffer); a.image_buffer = bytes_of(imageBuffer);
     a.dL_dpix = ptr(dL);
     a.dL_dmean2D = g.means2D.data_ptr<float>(); a.dL_dconic = const_cast<float*>(ptr(dL_dconic));
-    a.dL_dopacity = g.opacity.data_ptr<float>(); a.dL_dcolor = g.colors.data_ptr<float>(); a.dL_dmean3D = g.means3D.data_ptr<float>();
-    a.dL_dcov3D = g.cov3D.data_ptr<float>(); a.dL_dsh = M ? g.sh.data_ptr<float>() : nullptr; a.dL_dscale = g.scales.data_ptr<float>();
+    a.dL_dopacity = g.opacity.data_ptr<float>(); a.dL_dcolor = const_cast<float*>(ptr(g.colors)); a.dL_dmean3D = g.means3D.data_ptr<float>();
+    a.dL_dcov3D = const_cast<float*>(ptr(g.cov3D)); a.dL_dsh = M ? g.sh.data_ptr<float>() : nullptr; a.dL_dscale = g.scales.data_ptr<float>();
     a.dL_drot = g.rotations.data_ptr<float>();
     if (tone.given) a.tone = &tone.t;
     wg_second_image second{};
@@ -394,13 +400,14 @@ py::tuple RasterizeGaussiansBackwardEx(const torch::Tensor& background, const to
                                        const torch::Tensor& dL_dout_color, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
                                        const torch::Tensor& geomBuffer, const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
                                        const bool debug, const py::object& sh_tone, const OptTensor& dL_dout_color2, const py::object& raw_in,
-                                       const py::object& sh_second, const std::tuple<int, int, int>& options) {
+                                       const py::object& sh_second, const std::tuple<int, int, int>& options, const bool want_colors,
+                                       const bool want_cov3D) {
     const Scene s{background, means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, kernel_size,
                   opt(subpixel_offset), sh, degree, campos, debug};
     const Gradients g = backward(s, radii, dL_dout_color, geomBuffer, R, binningBuffer, imageBuffer, sh_tone, dL_dout_color2, raw_in, sh_second,
-                                 call_options(options));
+                                 call_options(options), false, want_colors, want_cov3D);
     py::list out;
-    for (const auto& t : g.eight()) out.append(t);
+    for (const auto& t : g.eight()) out.append(or_none(t));   // (None: dL_dcolors / dL_dcov3D that the caller did not want)
     if (!sh_second.is_none()) {
         for (const auto& t : {g.mul, g.offset, g.mul2, g.offset2}) out.append(or_none(t));
     } else if (dL_dout_color2.has_value()) {
@@ -409,6 +416,20 @@ py::tuple RasterizeGaussiansBackwardEx(const torch::Tensor& background, const to
         out.append(or_none(g.mul)); out.append(or_none(g.offset));
     }
     return py::tuple(out);
+}
+
+// (callers from before the two "wanted" flags: all eight)
+py::tuple RasterizeGaussiansBackwardExAll(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& colors,
+                                          const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier,
+                                          const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix,
+                                          const float tan_fovx, const float tan_fovy, const float kernel_size, const OptTensor& subpixel_offset,
+                                          const torch::Tensor& dL_dout_color, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
+                                          const torch::Tensor& geomBuffer, const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
+                                          const bool debug, const py::object& sh_tone, const OptTensor& dL_dout_color2, const py::object& raw_in,
+                                          const py::object& sh_second, const std::tuple<int, int, int>& options) {
+    return RasterizeGaussiansBackwardEx(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
+                                        tan_fovy, kernel_size, subpixel_offset, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
+                                        debug, sh_tone, dL_dout_color2, raw_in, sh_second, options, true, true);
 }
 
 // the colour-only backward pass (wg_backward_args::colour_gradients_only; _C.py refuses the calls it does not serve in front of both
@@ -433,6 +454,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {   // ext.cpp:15-19
     m.def("mark_visible", &markVisible);
     m.def("rasterize_gaussians_ex", &RasterizeGaussiansEx);                    // + the blocks of wg_forward_args, + the forward_only hint
     m.def("rasterize_gaussians_ex", &RasterizeGaussiansExNoHint);              //   (overload without the hint)
-    m.def("rasterize_gaussians_backward_ex", &RasterizeGaussiansBackwardEx);   // + the blocks of wg_backward_args
+    m.def("rasterize_gaussians_backward_ex", &RasterizeGaussiansBackwardEx);   // + the blocks of wg_backward_args, + which of dL_dcolors / dL_dcov3D the caller wants
+    m.def("rasterize_gaussians_backward_ex", &RasterizeGaussiansBackwardExAll);   //   (overload without the two flags: all eight)
     m.def("rasterize_gaussians_backward_colour", &RasterizeGaussiansBackwardColour);   // wg_backward_args::colour_gradients_only
 }

@@ -426,9 +426,12 @@ hipError_t launch_tile_sort(const ImageState& img, const BinningState& b, const 
                             const BinStats* guard, hipStream_t stream);
 // order_table != nullptr: img.order_fwd / img.order_key are valid (launch_forward_order ran): tiles launch in that order and write their
 // walked lengths back into the camera's row of the table
+// record_clear != nullptr: every wave zeroes its share of these floats (the frame's gradient record, rounded up to whole float4s as
+// launch_tile_order rounds them: 16-byte aligned, carved to a whole float4) as its last act, whatever the guard says
 hipError_t launch_render_forward(int W, int H, int gx, int gy, const ImageState& img, const BinningState& b,
                                  const GeometryState& g, const float* subpixel_offset, const float* background,
-                                 float* out_color, float* out_color2, bool lazy, bool exact, const BinStats* guard, uint32_t* order_table,
+                                 float* out_color, float* out_color2, bool lazy, bool exact, const BinStats* guard, float* record_clear,
+                                 size_t record_floats, uint32_t* order_table,
                                  uint32_t order_slots, uint32_t order_stride, hipStream_t stream);
 // the compositing of a frame whose binning and per-pixel stops are known (img.tile_last, img.n_contrib of an earlier pass over the
 // same geometry): each tile walks exactly its list's first tile_last entries and stores final outputs

@@ -578,8 +578,11 @@ def _forward_ctypes(background, means3D, colors, opacity, scales, rotations, sca
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, kernel_size, subpixel_offset, dL_dout_color, sh,
                                  degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, sh_tone=None, dL_dout_color2=None, raw=None,
-                                 sh_second=None, options=None, colour_gradients_only=None):
+                                 sh_second=None, options=None, colour_gradients_only=None, want=None):
     """The reference's `rasterize_gaussians_backward` (rasterize_points.h:42-66) -> the eight tensors, plus by keyword:
+    want = (dL_dcolors, dL_dcov3D) booleans (None = both): whether the caller reads them.  One it does not want comes back as None wherever the
+      library treats it as an intermediate (dL_dcolors with SH colours and the gradient record, dL_dcov3D without cov3D_precomp): it is then
+      neither allocated nor stored (wg_backward_args: NULL).  The autograd function passes its needs_input_grad.
     sh_tone: two more tensors are appended, dL_dsh_mul, dL_dsh_offset (None where the input was None); dL_dsh is then the gradient of the raw
       coefficients.
     sh_second (a frame rasterized with sh_second; needs dL_dout_color2): the eight + (dL_dsh_mul, dL_dsh_offset, dL_dsh_mul2, dL_dsh_offset2).
@@ -592,6 +595,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     global _reuse_epoch
     opts = resolve_call_options(options)
     colour_only = resolve_colour_gradients_only(colour_gradients_only)
+    want_colors, want_cov3D = (True, True) if want is None else (bool(want[0]), bool(want[1]))
     _reuse_epoch += 1   # what the forward calls remembered ends here (see "Geometry reuse" above) ...
     states = _PerThread._states
     for st in list(states.values()):                     # ... and so do the references that kept those frames' scratch alive (any thread's)
@@ -623,16 +627,16 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         return _torch_ext.rasterize_gaussians_backward_ex(background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
                                                           viewmatrix, projmatrix, float(tan_fovx), float(tan_fovy), float(kernel_size), subpixel_offset,
                                                           dL_dout_color, sh, int(degree), campos, geomBuffer, int(R), binningBuffer, imageBuffer,
-                                                          bool(debug), sh_tone, dL_dout_color2, raw, sh_second, opts)
+                                                          bool(debug), sh_tone, dL_dout_color2, raw, sh_second, opts, want_colors, want_cov3D)
     _check_backward_arguments(means3D, radii, colors, scales, rotations, cov3D_precomp, sh, dL_dout_color, sh_tone, dL_dout_color2, raw, sh_second)
     return _backward_ctypes(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
                             tan_fovy, kernel_size, subpixel_offset, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug,
-                            sh_tone, dL_dout_color2, raw, sh_second, opts)
+                            sh_tone, dL_dout_color2, raw, sh_second, opts, want_colors, want_cov3D)
 
 
 def _backward_ctypes(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                      kernel_size, subpixel_offset, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, sh_tone,
-                     dL_dout_color2, raw, sh_second, opts):
+                     dL_dout_color2, raw, sh_second, opts, want_colors=True, want_cov3D=True):
     """The checked backward call through ctypes -> the reference's eight, + what the optional blocks add."""
     device, P, H, W = means3D.device, means3D.size(0), dL_dout_color.size(1), dL_dout_color.size(2)
     sh = _f32(sh, device)
@@ -644,13 +648,16 @@ def _backward_ctypes(background, means3D, radii, colors, scales, rotations, scal
     f = dict(dtype=torch.float32, device=device)
     if P != 0 and (opts[2] or opts[1]):
         dL_dconic = None   # the reference's intermediate: not returned (rasterize_points.cu:201), so not requested
-        dL_dmeans2D, dL_dopacity, dL_dcolors = torch.empty((P, 3), **f), torch.empty((P, 1), **f), torch.empty((P, 3), **f)
+        dL_dmeans2D, dL_dopacity = torch.empty((P, 3), **f), torch.empty((P, 1), **f)
+        # (with SH colours an intermediate too: a caller that does not want it gets None, the kernel skips the store)
+        dL_dcolors = torch.empty((P, 3), **f) if want_colors or M == 0 else None
     else:
         acc = torch.zeros((P * 11,), **f)
         dL_dconic, dL_dmeans2D = acc[0:4 * P].view(P, 2, 2), acc[4 * P:7 * P].view(P, 3)
         dL_dcolors, dL_dopacity = acc[7 * P:10 * P].view(P, 3), acc[10 * P:11 * P].view(P, 1)
     alloc = torch.empty if P != 0 else torch.zeros
-    dL_dmeans3D, dL_dcov3D, dL_dsh = alloc((P, 3), **f), alloc((P, 6), **f), alloc((P, M, 3), **f)
+    dL_dmeans3D, dL_dsh = alloc((P, 3), **f), alloc((P, M, 3), **f)
+    dL_dcov3D = alloc((P, 6), **f) if want_cov3D or cov3D_precomp.numel() != 0 else None   # (from scales and rotations: an intermediate)
     alloc_sr = alloc if scales.numel() != 0 else torch.zeros
     dL_dscales, dL_drotations = alloc_sr((P, 3), **f), alloc_sr((P, 4), **f)
     dL_dcolors2 = alloc((P, 3), **f) if dual else None

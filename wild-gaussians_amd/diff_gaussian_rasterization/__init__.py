@@ -164,6 +164,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         if ctx.colour_only:   # dL_dcolors and nothing else: the geometry inputs' .grad stay as they were
             g_colors = _call_native(lambda *a: _C.rasterize_gaussians_backward(*a, **extra), native_args, rs.debug, "snapshot_bw.dump", "backward")[1]
             return (None, None, None, g_colors) + (None,) * 20
+        # dL_dcolors / dL_dcov3D are intermediates of a plain SH + scales/rotations call: wanted only where the input takes a gradient (what is not
+        # wanted comes back as None, neither allocated nor stored)
+        extra["want"] = (ctx.needs_input_grad[3], ctx.needs_input_grad[7])
         if ctx.sh_tone is not None:
             extra["sh_tone"] = ctx.sh_tone
         if ctx.raw:
