@@ -41,6 +41,17 @@ needs the few-line edits INTEGRATION.md lists.  What IS swapped, each with the r
                         through the model's own `_get_dino_cached`.  Calls it does not cover (another uncertainty_mode,
                         uncertainty_dino_max_size set, CPU tensors, a batch, a prediction that requires grad, an initialised process
                         group, a head of another form) go to the original method
+  uncertainty_backbone  (OFF by default: results move within float32 rounding)
+                        `UncertaintyModel._get_dino_cached` (method.py:257-265) -> the same statements, except that a covered backbone call
+                        (`dinov2_vits14_reg`'s architecture in float32 on a HIP device, a float32 [B, 3, 14 h, 14 w] input; wg_fused_dino) is
+                        served by a wg_fused_dino.DinoFeatures kept on the model object: blocks 0..num_heads - 1 only, attention with an online
+                        softmax, no N x N tensor.  The cache keeps the reference's keys, shapes and contents (`.detach().cpu()` stays).  Every
+                        uncovered call reaches the original method with the caller's arguments.  Composes with `uncertainty_loss` (which calls
+                        the model's `_get_dino_cached`) and with keep_training_frames_on_device(features=True)
+  uncertainty_feature_cache  (OFF by default: it changes memory use, 15.2 MB per 1600x1200 frame; only with uncertainty_backbone, else ValueError)
+                        a stored entry is ALSO registered under the key the reference looks up, (cache_entry, input shape) -- the same tensor
+                        object, no second copy -- so a frame's ground-truth features are computed once instead of at every visit.  No result
+                        changes: the fused extractor is bit-reproducible, the cached tensor is the recomputed one
   appearance_mlp        (OFF by default: results move within float32 rounding)
                         `EmbeddingModel.forward` (method.py:890-900) -> wg_fused_gaussians.embedding_forward: `cat`, the three Linear
                         layers, both ReLUs and `* 0.01` as one float32 MFMA kernel forward and one backward that recomputes the hidden
@@ -84,8 +95,8 @@ import torch
 
 def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True, densification_stats: bool = True, activations: bool = True,
                  eval_sh: bool = True, geometry_reuse: bool = True, edited_module=None, filter_3d: bool = False, densify: bool = False,
-                 embedding_optim: bool = False, uncertainty_loss: bool = False, appearance_mlp: bool = False,
-                 uncertainty_metrics: bool = False):
+                 embedding_optim: bool = False, uncertainty_loss: bool = False, uncertainty_backbone: bool = False,
+                 uncertainty_feature_cache: bool = False, appearance_mlp: bool = False, uncertainty_metrics: bool = False):
     """-> a function that restores everything that was replaced.  `model`: an already constructed GaussianModel (e.g.
     `WildGaussians(...).model`) whose existing optimizer should be adopted too.
     edited_module (default None): a module object holding a copy of the caller with INTEGRATION.md section 5's edit of `_render_internal`
@@ -93,6 +104,9 @@ def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True
     handed the swapped `ssim` / `eval_sh`."""
     import wg_fused_gaussians as FG
     import wg_fused_ssim
+    if uncertainty_feature_cache and not uncertainty_backbone:
+        raise ValueError("uncertainty_feature_cache needs uncertainty_backbone: only the fused extractor is bit-reproducible, so that a cached "
+                         "feature map is the one a recomputation would give")
     saved = []
 
     def swap(obj, name, new):
@@ -224,6 +238,39 @@ def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True
         def _compute_losses(self, gt, prediction, prefix='', _cache_entry=None):
             return wg_fused_uncertainty.compute_losses(self, gt, prediction, prefix, _cache_entry=_cache_entry, original=orig_compute_losses)
         swap(UM, "_compute_losses", _compute_losses)
+
+    if uncertainty_backbone:
+        import wg_fused_dino
+        UM = method_module.UncertaintyModel
+        orig_get_dino_cached = UM._get_dino_cached
+
+        def extractor_for(self, x):
+            """The model's DinoFeatures (one per backbone object, kept on the model) when backbone and tensor are the covered case, else None."""
+            backbone = getattr(self, "backbone", None)
+            ex = self.__dict__.get("_wg_dino_features")
+            if ex is None or ex.backbone is not backbone:
+                if not wg_fused_dino.DinoFeatures.covers(backbone, x):
+                    return None
+                ex = self.__dict__["_wg_dino_features"] = wg_fused_dino.DinoFeatures(backbone)
+            return ex if ex.input_covered(x) else None
+
+        def _get_dino_cached(self, x, cache_entry=None):
+            extractor = extractor_for(self, x)
+            if extractor is None:
+                return orig_get_dino_cached(self, x, cache_entry)   # the caller's own code, not a fallback of this library
+            if cache_entry is None or (cache_entry, x.shape) not in self._images_cache:
+                input_shape = x.shape
+                with torch.no_grad():
+                    x = extractor.features(x)   # the caller's self.backbone.get_intermediate_layers(x, n=[num_heads - 1], reshape=True)[-1]
+                if cache_entry is not None:
+                    stored = x.detach().cpu()
+                    self._images_cache[(cache_entry, x.shape)] = stored
+                    if uncertainty_feature_cache:
+                        self._images_cache[(cache_entry, input_shape)] = stored   # the key the look-up above asks for; the same object
+            else:
+                x = self._images_cache[(cache_entry, x.shape)].to(x.device)
+            return x
+        swap(UM, "_get_dino_cached", _get_dino_cached)
 
     if appearance_mlp:
         EM = method_module.EmbeddingModel
