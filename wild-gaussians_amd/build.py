@@ -57,13 +57,16 @@ SOURCES = {
                                                     # restates NumPy op for op: no contraction, no fast-math flag
     "dino/vit.hip": [],                # fused frozen DINOv2 ViT-S/14 feature extractor on float32 MFMA (include/wg_dino.h); no fast-math flag:
                                        # erf, the softmax's exp2 and the LayerNorm's division and square root keep their full precision
+    "lpips/lpips.hip": ["-ffp-contract=off"],   # fused LPIPS v0.1 on the AlexNet / VGG16 trunks: implicit-GEMM convolutions on float32 MFMA, max
+                                                # pool, head (include/wg_lpips.h); no fast-math flag, no contraction: the first layer's scaling
+                                                # chain and the head are the caller's float32 operations, rounded one by one
 }
 HEADERS = ["wg_common.h", "wg_alpha.h", "wg_sort.h", "wg_act.h", os.path.join(INCLUDE, "wg_rasterizer.h"), os.path.join(INCLUDE, "wg_knn.h"),
            os.path.join(INCLUDE, "wg_ssim.h"), os.path.join(INCLUDE, "wg_activations.h"), os.path.join(INCLUDE, "wg_densify.h"), os.path.join(INCLUDE, "wg_adam.h"), os.path.join(INCLUDE, "wg_sh_eval.h"),
            os.path.join(INCLUDE, "wg_filter3d.h"), os.path.join(INCLUDE, "wg_densify_prune.h"), os.path.join(INCLUDE, "wg_msssim.h"),
            os.path.join(INCLUDE, "wg_appearance_mlp.h"), os.path.join(INCLUDE, "wg_appearance_colour.h"),
            os.path.join(INCLUDE, "wg_uncertainty.h"), os.path.join(INCLUDE, "wg_frames.h"),
-           os.path.join(INCLUDE, "wg_metrics.h"), os.path.join(INCLUDE, "wg_dino.h")]
+           os.path.join(INCLUDE, "wg_metrics.h"), os.path.join(INCLUDE, "wg_dino.h"), os.path.join(INCLUDE, "wg_lpips.h")]
 
 
 def _newer(target: str, deps) -> bool:

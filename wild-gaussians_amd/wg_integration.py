@@ -87,6 +87,17 @@ And one on the EVALUATION module (`wildgaussians.evaluation`, not `method`), off
                         computes them), three doubles read back; LPIPS stays the module's own `lpips` / `lpips_vgg`.  Calls it does not cover
                         (anything but two uint8 / float32 NumPy arrays [..., H, W, C] with C <= 4 and H, W >= 11, no HIP device) go to the
                         original function
+
+And one more on the same module, off unless called (logged LPIPS values move within float32 rounding):
+
+    undo = wg_integration.fuse_evaluation_lpips(evaluation)           # any time: `lpips_alex` / `lpips_vgg` look `_lpips` up when called
+  evaluation LPIPS      `evaluation._lpips` (evaluation.py:255-291) -> the same result from wg_fused_lpips.LPIPS: both images through the AlexNet
+                        or VGG16 trunk as one batch of implicit-GEMM convolutions on float32 MFMA, clip / `* 2 - 1` / scaling layer applied
+                        while the first layer loads, one head kernel per tap, float64 pixel sums.  The network is the CALLER's: while
+                        `_LPIPS_CACHE` has no entry for `net` the call goes to the original function, which builds (downloads) and caches
+                        it; from then on a covered call reads that object's weights.  Calls it does not cover (anything but two float NumPy
+                        arrays of one shape [..., H, W, 3], a version other than "0.1", a module that is not the v0.1 alex / vgg model in eval
+                        mode and float32, H or W under 31 / 16, no HIP device) go to the original function with the caller's arguments
 """
 from __future__ import annotations
 
@@ -401,4 +412,74 @@ def fuse_evaluation_metrics(evaluation_module):
     def undo():
         if evaluation_module.compute_metrics is compute_metrics:
             evaluation_module.compute_metrics = original
+    return undo
+
+
+def fuse_evaluation_lpips(evaluation_module):
+    """Swap `evaluation_module._lpips` (the reference's wildgaussians/evaluation.py:255-291) for a wrapper over wg_fused_lpips.LPIPS.
+    -> a function that puts the original back.  Off unless called.
+
+    `lpips_alex` and `lpips_vgg` look `_lpips` up as a module global when they are called, so the swap reaches the original
+    `compute_metrics` and the one `fuse_evaluation_metrics` installs (which is handed `evaluation_module.lpips`) alike, whenever it is made.
+    No network is ever constructed here (the caller's constructor downloads its weights): while `evaluation_module._LPIPS_CACHE` has no entry
+    for `net`, the call goes to the original function, which builds and caches it.  From then on a covered call -- two float NumPy arrays of
+    one shape [..., H, W, 3], version "0.1", a cached module that wg_fused_lpips.structure_covered accepts, H and W at or above the net's
+    minimum (31 for alex, 16 for vgg), a HIP device -- is served by a wg_fused_lpips.LPIPS kept beside that cache entry (rebuilt when the entry
+    is another object).  Every other call reaches the original with the caller's arguments.  The result is float32, reshaped to the batch
+    shape, as the original returns it; values move within float32 rounding, which is why this is off unless called."""
+    import numpy as np
+    original = evaluation_module._lpips
+    fused = {}   # net -> (the cache entry it was built from, wg_fused_lpips.LPIPS or None for an uncovered module)
+
+    def parse(args, kwargs):
+        names = ("a", "b", "net", "version")
+        if len(args) > len(names) or set(kwargs) - set(names[len(args):]):
+            return None
+        given = dict(zip(names, args), **kwargs)
+        if not all(k in given for k in names[:3]):
+            return None
+        return given["a"], given["b"], given["net"], given.get("version", "0.1")
+
+    def served_by(a, b, net, version):
+        import wg_fused_lpips
+        if not (isinstance(a, np.ndarray) and isinstance(b, np.ndarray) and a.dtype.kind == "f" and b.dtype.kind == "f"):
+            return None
+        if a.shape != b.shape or a.ndim < 3 or a.shape[-1] != 3 or a.size == 0 or version != "0.1" or not isinstance(net, str):
+            return None
+        lp_net = getattr(evaluation_module, "_LPIPS_CACHE", {}).get(net)
+        if lp_net is None or not torch.cuda.is_available():
+            return None
+        entry = fused.get(net)
+        if entry is None or entry[0] is not lp_net:
+            covered = wg_fused_lpips.structure_covered(lp_net)
+            entry = fused[net] = (lp_net, wg_fused_lpips.LPIPS.from_module(lp_net) if covered else None)
+        op = entry[1]
+        if op is None or min(a.shape[-3], a.shape[-2]) < wg_fused_lpips.MIN_SIDE[op.net]:
+            return None
+        try:
+            op._fresh()   # the module may have left the covered case since (train mode, another dtype)
+        except RuntimeError:
+            return None
+        return op
+
+    def _lpips(*args, **kwargs):
+        parsed = parse(args, kwargs)
+        op = served_by(*parsed) if parsed is not None else None
+        if op is None:
+            return original(*args, **kwargs)   # the caller's own code, not a fallback of this library
+        a, b = parsed[0], parsed[1]
+        batch_shape, img_shape = a.shape[:-3], a.shape[-3:]
+        upload = lambda v: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).view(-1, *img_shape).to(op.device).permute(0, 3, 1, 2)
+        ta, tb = upload(a), upload(b)
+        if not op.input_covered(ta, tb):
+            return original(*args, **kwargs)
+        return op(ta, tb).cpu().numpy().reshape(batch_shape)
+
+    _lpips.__wrapped__ = original
+    evaluation_module._lpips = _lpips
+
+    def undo():
+        if evaluation_module._lpips is _lpips:
+            evaluation_module._lpips = original
+        fused.clear()
     return undo
