@@ -49,6 +49,8 @@ SOURCES = {
     "appearance/mlp.hip": [],          # fused appearance MLP fwd/bwd on float32 MFMA (include/wg_appearance_mlp.h); in a subdirectory: the
                                        # top level of csrc/ is the list of files bench.py's byte model names
     "appearance/colour.hip": [],       # fused toned-colour operator over mlp.hip's tile walk (include/wg_appearance_colour.h)
+    "appearance/rows.hip": [],         # the appearance MLP over a device-side list of visible rows, and the compaction that builds the list
+                                       # (include/wg_appearance_rows.h); mlp.hip's tile walk restated, so that mlp.hip compiles as before
     "uncertainty/uncertainty.hip": [],   # fused uncertainty head and DINO loss around the backbone (include/wg_uncertainty.h); in a
                                          # subdirectory for the same reason as appearance/
     "frames/frames.hip": [],           # device-resident training frames: uint8 store, fused unpack (include/wg_frames.h); no fast-math flag:
@@ -65,6 +67,7 @@ HEADERS = ["wg_common.h", "wg_alpha.h", "wg_sort.h", "wg_act.h", os.path.join(IN
            os.path.join(INCLUDE, "wg_ssim.h"), os.path.join(INCLUDE, "wg_activations.h"), os.path.join(INCLUDE, "wg_densify.h"), os.path.join(INCLUDE, "wg_adam.h"), os.path.join(INCLUDE, "wg_sh_eval.h"),
            os.path.join(INCLUDE, "wg_filter3d.h"), os.path.join(INCLUDE, "wg_densify_prune.h"), os.path.join(INCLUDE, "wg_msssim.h"),
            os.path.join(INCLUDE, "wg_appearance_mlp.h"), os.path.join(INCLUDE, "wg_appearance_colour.h"),
+           os.path.join(INCLUDE, "wg_appearance_rows.h"),
            os.path.join(INCLUDE, "wg_uncertainty.h"), os.path.join(INCLUDE, "wg_frames.h"),
            os.path.join(INCLUDE, "wg_metrics.h"), os.path.join(INCLUDE, "wg_dino.h"), os.path.join(INCLUDE, "wg_lpips.h")]
 

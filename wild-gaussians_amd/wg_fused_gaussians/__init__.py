@@ -42,6 +42,14 @@ activations and saves only its inputs (include/wg_appearance_mlp.h); no `cat`, t
     offset_mul = appearance_mlp((features[..., :3], gembedding), list(model.mlp.parameters()), shared=aembedding)   # [P, 6]
     toned = embedding_forward(model, gembedding, aembedding, features)                                              # EmbeddingModel.forward
 
+The same operator over the rows that reach the image only, forward and backward, with the list built on the device from the rasterizer's
+`radii` (no `nonzero`, no host synchronisation) and every value the bits of the dense operator on gathered inputs (include/wg_appearance_rows.h):
+
+    from wg_fused_gaussians import VisibleRows, appearance_rows
+    rows = VisibleRows.from_radii(radii)                      # or .from_mask(mask) / .from_index(index)
+    offset_mul = appearance_mlp((features[..., :3], gembedding), weights, shared=aembedding, rows=rows)             # [P, 6], zeros at unlisted rows
+    with appearance_rows(rows): ...                           # the forward that apply_optins(appearance_mlp=True) swaps in uses the list
+
 The toned precomputed colours of one image (method.py:1555, :1557, :890-900, :1592-1598) from its [E] appearance embedding in one kernel, with the
 embedding's gradient alone coming back in one kernel and a finishing launch, over the visible rows only (include/wg_appearance_colour.h); and the
 loop of optimize_embedding (method.py:1786-1815) around it:
@@ -52,7 +60,9 @@ loop of optimize_embedding (method.py:1786-1815) around it:
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import threading
 
 import torch
 
@@ -610,28 +620,35 @@ def _mlp_fill(args, inputs, shared, weights, out_scale, max_workgroups, stream):
     args.stream = stream
 
 
+def _mlp_operands(n_inputs, tensors):
+    """(inputs..., shared or None, W1 b1 W2 b2 W3 b3) as the autograd functions receive them -> checked and readable by the kernels:
+    (inputs, shared, weights, P, device)."""
+    inputs = [_mlp_row_view(t, f"inputs[{i}]") for i, t in enumerate(tensors[:n_inputs])]
+    shared = tensors[n_inputs]
+    weights = tensors[n_inputs + 1:]
+    P = inputs[0].shape[0]
+    dev = inputs[0].device
+    Kr = sum(t.shape[1] for t in inputs)
+    if any(t.shape[0] != P or t.device != dev for t in inputs):
+        raise RuntimeError("wg_fused_gaussians.appearance_mlp: inputs must have the same number of rows, on one device")
+    if shared is not None:
+        if not (shared.is_cuda and shared.dtype == torch.float32 and shared.dim() == 1 and shared.device == dev):
+            raise RuntimeError("wg_fused_gaussians.appearance_mlp: shared must be a 1-D float32 tensor on the inputs' device")
+        shared = shared.contiguous()
+    K = Kr + (0 if shared is None else shared.numel())
+    shapes = [(MLP_HIDDEN, K), (MLP_HIDDEN,), (MLP_HIDDEN, MLP_HIDDEN), (MLP_HIDDEN,), (MLP_OUT, MLP_HIDDEN), (MLP_OUT,)]
+    if len(weights) != 6 or any(not (w.is_cuda and w.dtype == torch.float32 and tuple(w.shape) == s and w.device == dev)
+                                for w, s in zip(weights, shapes)):
+        raise RuntimeError(f"wg_fused_gaussians.appearance_mlp: weights must be float32 (W1 b1 W2 b2 W3 b3) of shapes {shapes} on the "
+                           "inputs' device")
+    weights = [w.contiguous() for w in weights]
+    return inputs, shared, weights, P, dev
+
+
 class _AppearanceMlp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, n_inputs, out_scale, max_workgroups, *tensors):
-        inputs = [_mlp_row_view(t, f"inputs[{i}]") for i, t in enumerate(tensors[:n_inputs])]
-        shared = tensors[n_inputs]
-        weights = tensors[n_inputs + 1:]
-        P = inputs[0].shape[0]
-        dev = inputs[0].device
-        Kr = sum(t.shape[1] for t in inputs)
-        if any(t.shape[0] != P or t.device != dev for t in inputs):
-            raise RuntimeError("wg_fused_gaussians.appearance_mlp: inputs must have the same number of rows, on one device")
-        if shared is not None:
-            if not (shared.is_cuda and shared.dtype == torch.float32 and shared.dim() == 1 and shared.device == dev):
-                raise RuntimeError("wg_fused_gaussians.appearance_mlp: shared must be a 1-D float32 tensor on the inputs' device")
-            shared = shared.contiguous()
-        K = Kr + (0 if shared is None else shared.numel())
-        shapes = [(MLP_HIDDEN, K), (MLP_HIDDEN,), (MLP_HIDDEN, MLP_HIDDEN), (MLP_HIDDEN,), (MLP_OUT, MLP_HIDDEN), (MLP_OUT,)]
-        if len(weights) != 6 or any(not (w.is_cuda and w.dtype == torch.float32 and tuple(w.shape) == s and w.device == dev)
-                                    for w, s in zip(weights, shapes)):
-            raise RuntimeError(f"wg_fused_gaussians.appearance_mlp: weights must be float32 (W1 b1 W2 b2 W3 b3) of shapes {shapes} on the "
-                               "inputs' device")
-        weights = [w.contiguous() for w in weights]
+        inputs, shared, weights, P, dev = _mlp_operands(n_inputs, tensors)
         out = torch.empty((P, MLP_OUT), dtype=torch.float32, device=dev)
         args = _MlpArgs()
         _mlp_fill(args, inputs, shared, weights, out_scale, max_workgroups, torch.cuda.current_stream(dev).cuda_stream)
@@ -676,7 +693,143 @@ class _AppearanceMlp(torch.autograd.Function):
         return (None, None, None, *g_in, g_sh, *g_w)
 
 
-def appearance_mlp(inputs, weights, shared=None, out_scale=0.01, max_workgroups=0):
+# ---- the same operator over a list of rows (include/wg_appearance_rows.h, csrc/appearance/rows.hip) -------------------------------------
+class _RowsArgs(C.Structure):   # wg_appearance_rows_args
+    _fields_ = [("struct_size", C.c_size_t), ("mlp", _MlpArgs), ("rows", _vp), ("M", C.c_int64), ("rows_count", _vp)]
+
+
+_lib.wg_appearance_rows_scratch_floats.restype = C.c_int64
+_lib.wg_appearance_rows_scratch_floats.argtypes = [C.c_int64, C.c_int32]
+_lib.wg_appearance_rows_forward.restype = _i
+_lib.wg_appearance_rows_forward.argtypes = [C.POINTER(_RowsArgs)]
+_lib.wg_appearance_rows_backward.restype = _i
+_lib.wg_appearance_rows_backward.argtypes = [C.POINTER(_RowsArgs)]
+_lib.wg_appearance_rows_compact_scratch_bytes.restype = C.c_int64
+_lib.wg_appearance_rows_compact_scratch_bytes.argtypes = [C.c_int64]
+_lib.wg_appearance_rows_compact.restype = _i
+_lib.wg_appearance_rows_compact.argtypes = [C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]
+ROWS_COMPACT_BLOCK = 2048
+
+
+def appearance_rows_scratch_floats(capacity, max_workgroups=0):
+    """Floats of scratch a backward call over a list of this capacity needs (max_workgroups = 0 asks the current device)."""
+    return _native._check(_lib.wg_appearance_rows_scratch_floats(int(capacity), int(max_workgroups)), "wg_appearance_rows_scratch_floats")
+
+
+class VisibleRows:
+    """The rows `appearance_mlp(rows=)` evaluates: `index` (int32 on the device), `M` (a host number: the exact entry count, or the
+    capacity when `count` is given), `count` (None, or one int32 on the device: the real count) and `P` (the row count of the tensors the
+    list belongs to; None when unknown).  `from_radii` and `from_mask` build the list on the device in ascending order with NO host
+    synchronisation (include/wg_appearance_rows.h): the count stays on the device and M is the capacity P."""
+    __slots__ = ("index", "M", "count", "P")
+
+    def __init__(self, index, M, count=None, P=None):
+        if index.numel() == 0:   # the C-ABI refuses a null list; an empty one still has an address
+            index = torch.zeros(1, dtype=torch.int32, device=index.device)
+        self.index, self.M, self.count, self.P = index, int(M), count, (None if P is None else int(P))
+
+    @staticmethod
+    def _compact(flags, is_radii):
+        P = flags.numel()
+        dev = flags.device
+        index = torch.empty(P, dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            nbytes = _native._check(_lib.wg_appearance_rows_compact_scratch_bytes(P), "wg_appearance_rows_compact_scratch_bytes")
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ptr = flags.data_ptr() if P else None
+            _native._check(_lib.wg_appearance_rows_compact(P, ptr if is_radii else None, None if is_radii else ptr, index.data_ptr() if P else None,
+                                                           count.data_ptr(), scratch.data_ptr(), nbytes,
+                                                           torch.cuda.current_stream(dev).cuda_stream), "wg_appearance_rows_compact")
+        return VisibleRows(index, P, count, P)
+
+    @classmethod
+    def from_radii(cls, radii):
+        """Rows with radii > 0 (`radii`: the rasterizer's int32 [P])."""
+        if not (torch.is_tensor(radii) and radii.is_cuda and radii.dtype == torch.int32 and radii.dim() == 1):
+            raise RuntimeError("wg_fused_gaussians.VisibleRows.from_radii: radii must be a 1-D int32 tensor on a HIP device")
+        return cls._compact(radii.detach().contiguous(), True)
+
+    @classmethod
+    def from_mask(cls, mask):
+        """Rows whose mask byte is non-zero (`mask`: bool or uint8 [P]; a bool mask is viewed as uint8, not copied)."""
+        if not (torch.is_tensor(mask) and mask.is_cuda and mask.dtype in (torch.bool, torch.uint8) and mask.dim() == 1):
+            raise RuntimeError("wg_fused_gaussians.VisibleRows.from_mask: mask must be a 1-D bool or uint8 tensor on a HIP device")
+        mask = mask.detach().contiguous()
+        return cls._compact(mask.view(torch.uint8) if mask.dtype == torch.bool else mask, False)
+
+    @classmethod
+    def from_index(cls, index, P=None):
+        """An explicit list of row indices (int32 or int64, on the device), in any order; M is its length, a host number."""
+        if not (torch.is_tensor(index) and index.is_cuda and index.dtype in (torch.int32, torch.int64) and index.dim() == 1):
+            raise RuntimeError("wg_fused_gaussians.VisibleRows.from_index: index must be a 1-D int32 / int64 tensor on a HIP device")
+        return cls(index.detach().to(torch.int32).contiguous(), index.numel(), None, P)
+
+
+def _rows_fill(args, rows):
+    args.struct_size = C.sizeof(_RowsArgs)
+    args.rows = rows.index.data_ptr()
+    args.M = rows.M
+    args.rows_count = None if rows.count is None else rows.count.data_ptr()
+
+
+class _AppearanceMlpRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, n_inputs, out_scale, max_workgroups, rows, *tensors):
+        inputs, shared, weights, P, dev = _mlp_operands(n_inputs, tensors)
+        if rows.index.device != dev or (rows.count is not None and rows.count.device != dev) or rows.M > rows.index.numel():
+            raise RuntimeError("wg_fused_gaussians.appearance_mlp: rows must be on the inputs' device and hold M entries")
+        if rows.P is not None and rows.P != P:
+            raise RuntimeError(f"wg_fused_gaussians.appearance_mlp: the row list was built for {rows.P} rows, the inputs have {P}")
+        out = torch.zeros((P, MLP_OUT), dtype=torch.float32, device=dev)   # unlisted rows stay zero: the kernel writes listed rows only
+        args = _RowsArgs()
+        _mlp_fill(args.mlp, inputs, shared, weights, out_scale, max_workgroups, torch.cuda.current_stream(dev).cuda_stream)
+        _rows_fill(args, rows)
+        args.mlp.out = out.data_ptr()
+        with torch.cuda.device(dev):
+            _native._check(_lib.wg_appearance_rows_forward(C.byref(args)), "wg_appearance_rows_forward")
+        ctx.save_for_backward(*inputs, *([] if shared is None else [shared]), *weights)   # the inputs (and the list) and nothing else
+        ctx.rows = rows
+        ctx.n_inputs, ctx.has_shared, ctx.out_scale, ctx.max_workgroups = n_inputs, shared is not None, out_scale, max_workgroups
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        saved = ctx.saved_tensors
+        n = ctx.n_inputs
+        inputs = list(saved[:n])
+        shared = saved[n] if ctx.has_shared else None
+        weights = list(saved[n + (1 if ctx.has_shared else 0):])
+        need = ctx.needs_input_grad[4:]
+        need_in, need_sh, need_w = need[:n], need[n], any(need[n + 1:])
+        P, dev = inputs[0].shape[0], inputs[0].device
+        g_out = g_out.contiguous()
+        args = _RowsArgs()
+        _mlp_fill(args.mlp, inputs, shared, weights, ctx.out_scale, ctx.max_workgroups, torch.cuda.current_stream(dev).cuda_stream)
+        _rows_fill(args, ctx.rows)
+        m = args.mlp
+        m.dL_dout = g_out.data_ptr()
+        g_in = [torch.zeros((P, t.shape[1]), dtype=torch.float32, device=dev) if nd else None for t, nd in zip(inputs, need_in)]
+        for i, g in enumerate(g_in):
+            if g is not None:
+                m.grad_segment[i] = g.data_ptr()
+                m.grad_row_stride[i] = g.shape[1]
+        g_sh = torch.empty_like(shared) if (shared is not None and need_sh) else None
+        if g_sh is not None:
+            m.grad_shared = g_sh.data_ptr()
+        g_w = [torch.empty_like(w) for w in weights] if need_w else [None] * 6
+        if need_w:
+            m.dW1, m.db1, m.dW2, m.db2, m.dW3, m.db3 = [g.data_ptr() for g in g_w]
+        with torch.cuda.device(dev):
+            floats = appearance_rows_scratch_floats(ctx.rows.M, ctx.max_workgroups)
+            scratch = torch.empty(floats, dtype=torch.float32, device=dev)
+            m.scratch, m.scratch_floats = scratch.data_ptr(), floats
+            _native._check(_lib.wg_appearance_rows_backward(C.byref(args)), "wg_appearance_rows_backward")
+        g_w = [g if nd else None for g, nd in zip(g_w, need[n + 1:])]
+        return (None, None, None, None, *g_in, g_sh, *g_w)
+
+
+def appearance_mlp(inputs, weights, shared=None, out_scale=0.01, max_workgroups=0, rows=None):
     """-> [P, 6] = out_scale * (W3 . relu(W2 . relu(W1 . cat(inputs..., shared) + b1) + b2) + b3), one HIP kernel in float32 on the matrix
     cores; nothing but the inputs is saved for the backward pass, which recomputes the hidden activations (include/wg_appearance_mlp.h).
 
@@ -684,11 +837,48 @@ def appearance_mlp(inputs, weights, shared=None, out_scale=0.01, max_workgroups=
              `features[..., :3]`, is not copied); the widths sum to 1..64
     weights  (W1 [128, K], b1, W2 [128, 128], b2, W3 [6, 128], b3) as nn.Linear holds them, K = sum of widths (+ len(shared))
     shared   optional [E <= 64] vector that every row carries behind its own columns (the image's appearance embedding)
+    rows     optional VisibleRows: only the listed rows are evaluated, forward and backward (include/wg_appearance_rows.h).  The result is
+             [P, 6] with zeros at unlisted rows, input gradients are [P, w_i] with zeros at unlisted rows, and every value has the bits of
+             this operator run on `x[rows]` with the cotangent `g[rows]`.  None: all rows, the dense kernels
     Gradients go to whichever of inputs / shared / weights require them.  Two calls on the same inputs give the same bits."""
     inputs = list(inputs)
     if not 1 <= len(inputs) <= 3:
         raise RuntimeError("wg_fused_gaussians.appearance_mlp: one to three inputs")
-    return _AppearanceMlp.apply(len(inputs), float(out_scale), int(max_workgroups), *inputs, shared, *weights)
+    if rows is None:
+        return _AppearanceMlp.apply(len(inputs), float(out_scale), int(max_workgroups), *inputs, shared, *weights)
+    if not isinstance(rows, VisibleRows):
+        raise RuntimeError("wg_fused_gaussians.appearance_mlp: rows must be a VisibleRows (from_radii, from_mask or from_index)")
+    return _AppearanceMlpRows.apply(len(inputs), float(out_scale), int(max_workgroups), rows, *inputs, shared, *weights)
+
+
+_rows_context = threading.local()
+
+
+def current_appearance_rows():
+    """The VisibleRows of the innermost active `appearance_rows` block of this thread, or None."""
+    stack = getattr(_rows_context, "stack", None)
+    return stack[-1] if stack else None
+
+
+@contextlib.contextmanager
+def appearance_rows(rows):
+    """While active (in this thread), the `EmbeddingModel.forward` that wg_integration.apply_optins(appearance_mlp=True) swaps in evaluates
+    the listed rows only:
+
+        with appearance_rows(VisibleRows.from_radii(radii)):
+            colors_toned = self.appearance_mlp(...)
+
+    Blocks nest; leaving one restores the list of the enclosing block (none by default).  `rows` may be None: the dense operator inside."""
+    if rows is not None and not isinstance(rows, VisibleRows):
+        raise RuntimeError("wg_fused_gaussians.appearance_rows: rows must be a VisibleRows or None")
+    stack = getattr(_rows_context, "stack", None)
+    if stack is None:
+        stack = _rows_context.stack = []
+    stack.append(rows)
+    try:
+        yield rows
+    finally:
+        stack.pop()
 
 
 _SH_C0 = 0.28209479177387814
@@ -711,11 +901,13 @@ def _mlp_covered(module):
     return (l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias)
 
 
-def embedding_forward(module, gembedding, aembedding, color, viewdir=None, *, original_forward=None, max_workgroups=0):
+def embedding_forward(module, gembedding, aembedding, color, viewdir=None, *, original_forward=None, max_workgroups=0, rows=None):
     """EmbeddingModel.forward (wildgaussians/method.py:890-900) around the fused operator: `color[..., :3]`, `gembedding` and `aembedding`
     are read in place (no `cat`); an `aembedding` of shape [E] is the shared path, one of shape [P, E] the per-row path.  Calls the fused
     operator does not cover -- CPU tensors, a dtype other than float32, appearance_model_sh = True, an `mlp` of another shape -- go to the
-    module's own forward (`original_forward`, default type(module).forward): the caller's code, not a fallback of this library."""
+    module's own forward (`original_forward`, default type(module).forward): the caller's code, not a fallback of this library.
+    rows: an optional VisibleRows; the MLP then runs over the listed rows only and the toned result is 0 at every other row (its `mul` and
+    `offset` are), which is what a rasterizer call that culls those rows never reads.  A list built for another row count raises."""
     weights = _mlp_covered(module)
     tensors = (gembedding, aembedding, color)
     ok = (weights is not None and not getattr(getattr(module, "config", None), "appearance_model_sh", False)
@@ -728,10 +920,12 @@ def embedding_forward(module, gembedding, aembedding, color, viewdir=None, *, or
         fwd = original_forward if original_forward is not None else type(module).forward
         return fwd(module, gembedding, aembedding, color, viewdir)
     input_color = color
+    if rows is not None and rows.P is not None and rows.P != color.shape[0]:
+        raise RuntimeError(f"wg_fused_gaussians.embedding_forward: the row list was built for {rows.P} rows, color has {color.shape[0]}")
     if aembedding.dim() == 1:
-        om = appearance_mlp((color[..., :3], gembedding), weights, shared=aembedding, out_scale=0.01, max_workgroups=max_workgroups)
+        om = appearance_mlp((color[..., :3], gembedding), weights, shared=aembedding, out_scale=0.01, max_workgroups=max_workgroups, rows=rows)
     else:
-        om = appearance_mlp((color[..., :3], gembedding, aembedding), weights, out_scale=0.01, max_workgroups=max_workgroups)
+        om = appearance_mlp((color[..., :3], gembedding, aembedding), weights, out_scale=0.01, max_workgroups=max_workgroups, rows=rows)
     offset, mul = torch.split(om, [3, 3], dim=-1)
     offset = torch.cat((offset / _SH_C0, torch.zeros_like(input_color[..., 3:])), dim=-1)
     mul = mul.repeat(1, input_color.shape[-1] // 3)

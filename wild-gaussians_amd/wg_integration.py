@@ -58,7 +58,15 @@ needs the few-line edits INTEGRATION.md lists.  What IS swapped, each with the r
                         activations (nothing of size P x 128 is kept or written); the two toning statements stay torch.  An `aembedding`
                         of shape [E] takes the shared path.  Calls it does not cover (CPU tensors, a dtype other than float32,
                         appearance_model_sh = True, an `mlp` that is not Linear-ReLU-Linear-ReLU-Linear with 128 / 128 / 6) go to the
-                        original forward
+                        original forward.
+                        Over the visible rows only (off unless the caller asks): inside
+                            with wg_fused_gaussians.appearance_rows(wg_fused_gaussians.VisibleRows.from_radii(radii)):
+                        -- the one-line edit of `_render_internal` around method.py:1592, `radii` being what the raw call at :1574
+                        returned -- the swapped forward evaluates the rows with radii > 0 only, forward and
+                        backward, and returns zeros at the others, which the toned call of the same geometry never reads.  A list built
+                        for another row count raises; no list is ever guessed from an earlier rasterizer call.  The `two_tone`
+                        single-call edit has no `radii` before the MLP: it is either the two calls with `geometry_reuse` and the row
+                        list, or one call and the dense MLP
   edited_module         (off by default) `GaussianModel._render_internal` -> the one of a module the INTEGRATOR supplies: a copy of the caller with
                         INTEGRATION.md section 5's "two_colour" or "two_tone" edit applied (the documented diff is the deliverable; this package
                         does not rewrite anybody's source -- tests/real_caller/render_edits.py is the test tool that builds such a module in memory)
@@ -288,7 +296,8 @@ def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True
         orig_embedding_forward = EM.forward
 
         def embedding_forward(self, gembedding, aembedding, color, viewdir=None):
-            return FG.embedding_forward(self, gembedding, aembedding, color, viewdir, original_forward=orig_embedding_forward)
+            return FG.embedding_forward(self, gembedding, aembedding, color, viewdir, original_forward=orig_embedding_forward,
+                                        rows=FG.current_appearance_rows())
         swap(EM, "forward", embedding_forward)
 
     if embedding_optim:
