@@ -62,6 +62,13 @@ SOURCES = {
     "lpips/lpips.hip": ["-ffp-contract=off"],   # fused LPIPS v0.1 on the AlexNet / VGG16 trunks: implicit-GEMM convolutions on float32 MFMA, max
                                                 # pool, head (include/wg_lpips.h); no fast-math flag, no contraction: the first layer's scaling
                                                 # chain and the head are the caller's float32 operations, rounded one by one
+    "loss/step_loss.hip": [],          # fused train-step image loss: mask, multiplier schedule, loss and all logged metrics in ssim.hip's loss
+                                       # tile restated (include/wg_step_loss.h).  No fast-math flag: the divisions and log10 of the statistics
+                                       # stay correctly rounded.  Contraction is left at the compiler's default ON, on purpose: the stencil and
+                                       # the SSIM formula then have the instructions (and the bits) of ssim.hip's l1_ssim_loss, whose tolerances
+                                       # the tests reuse; the one place where the reference's bits are promised, the effective multiplier
+                                       # 1 + p * (m - 1), switches it off for itself with a pragma, and every statistic's term is rounded to
+                                       # float32 before it is widened into a float64 sum, which no contraction can cross
 }
 HEADERS = ["wg_common.h", "wg_alpha.h", "wg_sort.h", "wg_act.h", os.path.join(INCLUDE, "wg_rasterizer.h"), os.path.join(INCLUDE, "wg_knn.h"),
            os.path.join(INCLUDE, "wg_ssim.h"), os.path.join(INCLUDE, "wg_activations.h"), os.path.join(INCLUDE, "wg_densify.h"), os.path.join(INCLUDE, "wg_adam.h"), os.path.join(INCLUDE, "wg_sh_eval.h"),
@@ -69,7 +76,8 @@ HEADERS = ["wg_common.h", "wg_alpha.h", "wg_sort.h", "wg_act.h", os.path.join(IN
            os.path.join(INCLUDE, "wg_appearance_mlp.h"), os.path.join(INCLUDE, "wg_appearance_colour.h"),
            os.path.join(INCLUDE, "wg_appearance_rows.h"),
            os.path.join(INCLUDE, "wg_uncertainty.h"), os.path.join(INCLUDE, "wg_frames.h"),
-           os.path.join(INCLUDE, "wg_metrics.h"), os.path.join(INCLUDE, "wg_dino.h"), os.path.join(INCLUDE, "wg_lpips.h")]
+           os.path.join(INCLUDE, "wg_metrics.h"), os.path.join(INCLUDE, "wg_dino.h"), os.path.join(INCLUDE, "wg_lpips.h"),
+           os.path.join(INCLUDE, "wg_step_loss.h")]
 
 
 def _newer(target: str, deps) -> bool:

@@ -11,6 +11,10 @@ backward needs; one more kernel is the whole backward (include/wg_ssim.h, csrc/s
     from wg_fused_ssim import msssim, ssim_down    # the uncertainty model's two metrics (method.py:126-187), forward only
     m = msssim(gt, prediction, max_size=400, min_size=80)    # [B, H, W] in levels + 3 launches (include/wg_msssim.h, csrc/ssim.hip)
     s = ssim_down(gt, prediction, max_size=400)              # [B, H, W] in 3 launches
+
+    from wg_fused_ssim import step_loss, step_metrics    # the train step's loss with mask, multiplier schedule and all logged metrics
+    loss, stats = step_loss(image_toned, image, gt, 0.2, mask=mask, loss_mult=raw_mult, mult_threshold=1, mult_blend=p)   # method.py:1920-1965
+    loss.backward(); metrics.update(step_metrics(stats))     # method.py:1968-1992 in one host copy (include/wg_step_loss.h, csrc/loss/step_loss.hip)
 """
 from __future__ import annotations
 
@@ -44,6 +48,13 @@ _lib.wg_ssim_down_scratch_floats.restype = C.c_size_t
 _lib.wg_ssim_down_scratch_floats.argtypes = [_i] * 4
 _lib.wg_ssim_down_forward.restype = _i
 _lib.wg_ssim_down_forward.argtypes = [_i] * 7 + [_vp] * 5
+_d = C.c_double
+_lib.wg_step_loss_scratch_floats.restype = C.c_size_t
+_lib.wg_step_loss_scratch_floats.argtypes = [_i, _i, _i]
+_lib.wg_step_loss_forward.restype = _i
+_lib.wg_step_loss_forward.argtypes = [_i, _i, _i] + [_vp] * 5 + [_i, _f, _f, _d] + [_vp] * 7
+_lib.wg_step_loss_backward.restype = _i
+_lib.wg_step_loss_backward.argtypes = [_i, _i, _i] + [_vp] * 5 + [_i, _f, _f, _d] + [_vp] * 7
 
 
 def _check(img):
@@ -177,6 +188,113 @@ def l1_ssim_loss(img_l1: torch.Tensor, img_ssim: torch.Tensor, gt: torch.Tensor,
     (l1_mean, ssim_mean) the reference logs (method.py:1970-1972)."""
     loss, parts = _L1SSIMLoss.apply(img_l1, img_ssim, gt, lambda_dssim, loss_mult)
     return (loss, parts[0], parts[1]) if return_parts else loss
+
+
+# The entries of step_loss's stats vector (include/wg_step_loss.h: enum wg_step_stat), in order.
+STEP_STATS = ("loss", "l1_loss", "ssim", "mse", "psnr", "l1_weighted", "dssim_weighted", "mask_percentage", "ssim_masked", "mse_masked",
+              "psnr_masked", "l1_loss_masked")
+_STEP_LOGGED = ("l1_loss", "ssim", "mse", "loss", "psnr")                                                   # method.py:1971-1977
+_STEP_LOGGED_MASKED = ("mask_percentage", "ssim_masked", "mse_masked", "psnr_masked", "l1_loss_masked")     # method.py:1986-1992
+
+
+def _plane(name, t, H, W):
+    """A [H, W] or [1, H, W] float32 constant as a contiguous [H*W] plane."""
+    _check(t)
+    if t.requires_grad:
+        raise RuntimeError(f"wg_fused_ssim.step_loss: {name} is a constant; detach it")
+    if tuple(t.shape) not in ((H, W), (1, H, W)):
+        raise RuntimeError(f"wg_fused_ssim.step_loss: {name} must be [H, W] or [1, H, W] = [{H}, {W}], got {list(t.shape)}")
+    return t.reshape(H, W).contiguous()
+
+
+class _StepLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img_l1, img_ssim, gt, lambda_dssim, mask, loss_mult, mult_threshold, mult_blend, grad_mode):
+        for t in (img_l1, img_ssim, gt):
+            _check(t)
+        if not (img_l1.shape == img_ssim.shape == gt.shape) or gt.dim() != 3:
+            raise RuntimeError("wg_fused_ssim.step_loss: three [C, H, W] images of the same shape are expected")
+        if gt.requires_grad:
+            raise RuntimeError("wg_fused_ssim.step_loss: the ground truth is a constant; detach it")
+        same = img_l1 is img_ssim
+        a = img_l1.contiguous()
+        b = a if same else img_ssim.contiguous()
+        g = gt.contiguous()
+        Cn, H, W = g.shape
+        k = None if mask is None else _plane("mask", mask, H, W)
+        m = None if loss_mult is None else _plane("loss_mult", loss_mult, H, W)
+        n = _lib.wg_step_loss_scratch_floats(Cn, H, W)
+        if n == 0:
+            raise RuntimeError(f"wg_fused_ssim.step_loss: unsupported sizes ({Cn} x {H} x {W})")
+        # grad_mode: the caller's torch.is_grad_enabled() (inside forward it is always off, and needs_input_grad ignores it): under no_grad
+        # no derivative maps are allocated or written
+        need = grad_mode and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        dev = g.device
+        d = torch.empty((3, Cn, H, W), device=dev, dtype=torch.float32) if need else None
+        scratch = torch.empty((n // 2,), device=dev, dtype=torch.float64)   # float64 partial sums: n float32 words, 8-byte aligned
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        stats = torch.empty((len(STEP_STATS),), device=dev, dtype=torch.float64)
+        ctx.mult_args = (int(mult_threshold is not None), float(0.0 if mult_threshold is None else mult_threshold), float(mult_blend),
+                         float(lambda_dssim))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        with torch.cuda.device(dev):
+            _native._check(_lib.wg_step_loss_forward(Cn, H, W, a.data_ptr(), b.data_ptr(), g.data_ptr(), ptr(k), ptr(m), *ctx.mult_args,
+                                                     scratch.data_ptr(), loss.data_ptr(), stats.data_ptr(),
+                                                     d[0].data_ptr() if need else None, d[1].data_ptr() if need else None,
+                                                     d[2].data_ptr() if need else None, stream), "wg_step_loss_forward")
+        ctx.same, ctx.have_maps, ctx.have_mask, ctx.have_mult = same, need, k is not None, m is not None
+        if need:
+            none = torch.empty(0, device=dev)
+            ctx.save_for_backward(a, b, g, d, none if k is None else k, none if m is None else m)
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_stats):
+        if not ctx.have_maps:
+            return (None,) * 9
+        a, b, g, d, k, m = ctx.saved_tensors
+        Cn, H, W = g.shape
+        gl = grad_loss.contiguous().reshape(1).float()
+        ga = torch.empty_like(a)
+        gb = ga if ctx.same else torch.empty_like(b)
+        stream = torch.cuda.current_stream(g.device).cuda_stream
+        with torch.cuda.device(g.device):
+            _native._check(_lib.wg_step_loss_backward(Cn, H, W, a.data_ptr(), b.data_ptr(), g.data_ptr(), k.data_ptr() if ctx.have_mask else None,
+                                                      m.data_ptr() if ctx.have_mult else None, *ctx.mult_args, gl.data_ptr(), d[0].data_ptr(),
+                                                      d[1].data_ptr(), d[2].data_ptr(), ga.data_ptr(), gb.data_ptr(), stream),
+                           "wg_step_loss_backward")
+        if ctx.same:   # autograd adds the two returned gradients of the one tensor: hand the sum over once
+            return (ga,) + (None,) * 8
+        return (ga, gb) + (None,) * 7
+
+
+def step_loss(image_toned: torch.Tensor, image: torch.Tensor, gt: torch.Tensor, lambda_dssim: float = 0.2, *, mask=None, loss_mult=None,
+              mult_threshold=None, mult_blend: float = 1.0):
+    """The reference's train step between the render and loss.backward(), and the logging block behind it (wildgaussians/method.py:1920-1992,
+    uncertainty_scale_grad and uncertainty_center_mult off), in two launches forward and one backward, with no host synchronisation:
+
+        image, image_toned = scale_grads(image, mask), scale_grads(image_toned, mask)       # when mask is given: gradients * mask
+        m = loss_mult;  m = (m > mult_threshold).float() when mult_threshold is given;  m = 1 + mult_blend * (m - 1)
+        loss = (1 - lambda_dssim) * (|image_toned - gt| * m).mean() + lambda_dssim * ((1 - ssim(image, gt, size_average=False)) * m).mean()
+
+    image_toned is the appearance-toned render, image the raw one (pass the same tensor twice when there is only one); gt, mask and loss_mult
+    ([H, W] or [1, H, W]) are constants.  The reference's schedule (method.py:1934-1940) is mult_threshold=1 with mult_blend = 0 before the
+    warm-up, p during it and 1 after it; mult_threshold=None, mult_blend=1 passes a ready-made multiplier through untouched.
+    Returns (loss, stats): the differentiable float32 scalar and the float64 device vector of STEP_STATS, which step_metrics reads."""
+    return _StepLoss.apply(image_toned, image, gt, lambda_dssim, mask, loss_mult, mult_threshold, mult_blend, torch.is_grad_enabled())
+
+
+def step_metrics(stats: torch.Tensor, prefix: str = "") -> dict:
+    """The reference's logged metrics (method.py:1971-1992, without num_gaussians) as Python floats, from step_loss's stats vector in ONE
+    device-to-host copy.  The five masked entries appear exactly when step_loss was given a mask."""
+    v = stats.detach().cpu().tolist()
+    if len(v) != len(STEP_STATS):
+        raise ValueError(f"wg_fused_ssim.step_metrics: a stats vector of {len(STEP_STATS)} entries is expected")
+    by_name = dict(zip(STEP_STATS, v))
+    names = _STEP_LOGGED + (_STEP_LOGGED_MASKED if not math.isnan(by_name["mask_percentage"]) else ())
+    return {prefix + n: by_name[n] for n in names}
 
 
 def _area_size(H: int, W: int, scale_factor: float):
