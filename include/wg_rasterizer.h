@@ -274,6 +274,33 @@ const char* wg_status_string(int status);
 const char* wg_last_hip_error(void);
 const char* wg_version(void);
 
+/* ---- the projection-only pass: a frame's cull decisions before (and without) rendering it ----
+ * radii[i] with THE BITS a forward call writes for the same geometry inputs and camera (0 = culled: behind the near plane at view-space
+ * z <= 0.2, a singular 2-D covariance, or a tile rectangle that misses the grid), so radii > 0 is the set of Gaussians that reach the
+ * image.  It is the per-Gaussian kernel's geometry restated (near cull, projection, 3-D covariance, clamped EWA Jacobian, mip filter,
+ * eigenvalue radius, ndc2Pix, getRect), built with that kernel's flags.  wg_mark_visible is NOT this: it is the near-plane test alone.
+ * One launch on `stream`; no colour, no SH block, no geometry / binning / image buffer, no allocator, no atomics, no host wait: it can be
+ * captured.  Reads 12 + 12 + 16 bytes per Gaussian (12 + 24 with cov3D_precomp; + 4 with filter_3D), writes radii[0 .. P) in full and
+ * nothing else.  `prefiltered` is not an input: the pass never traps.
+ *   scales + rotations XOR cov3D_precomp, as in the forward call.
+ *   filter_3D (only with scales + rotations): those two are then the caller's RAW parameters (wg_raw_gaussians) and get_gaussians() runs
+ *     in-kernel.  There is no raw_opacities field: of the activation's outputs only the normalised rotation and sqrt(exp(ls)^2 + f^2)
+ *     reach the radius; the opacity reaches neither, so it is not read.
+ * WG_ERR_INVALID_ARGUMENT, before any device work: struct_size smaller than the struct, P < 0, width or height <= 0, with P > 0 a NULL
+ * means3D / viewmatrix / projmatrix / radii or both / neither covariance source (or half a scales + rotations pair), filter_3D together
+ * with cov3D_precomp.  P = 0 returns WG_OK and launches nothing.  Fields are only ever appended. */
+typedef struct wg_project_args {
+    size_t struct_size;   /* the CALLER's sizeof(wg_project_args) */
+    int P, width, height;
+    const float *means3D, *scales, *rotations, *cov3D_precomp;
+    const float* filter_3D;   /* [P] or NULL */
+    float scale_modifier, tan_fovx, tan_fovy, kernel_size;
+    const float *viewmatrix, *projmatrix;
+    int* radii;               /* [P], fully overwritten */
+    void* stream;
+} wg_project_args;
+int wg_project_radii(const wg_project_args* args);
+
 #ifdef __cplusplus
 }
 #endif

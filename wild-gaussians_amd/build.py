@@ -32,6 +32,9 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-
 # per-file extra flags: the preprocess kernel must not fuse multiply-adds (integer outputs bit-exact vs oracle)
 SOURCES = {
     "preprocess.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
+    "project/project.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],   # the projection-only pass (wg_project_radii): preprocess.hip's
+                                                                           # geometry restated under preprocess.hip's flags, so that radii has
+                                                                           # the forward call's bits; in a subdirectory like the other opt-ins
     "binning.hip": ["-fno-slp-vectorize"],
     "render_fwd.hip": ["-fno-slp-vectorize"],
     "render_bwd.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],

@@ -1373,6 +1373,38 @@ int wg_mark_visible(int P, const float* means3D, const float* viewmatrix, const 
     return WG_OK;
 }
 
+// The projection-only pass: one launch on the caller's stream, no buffer, no allocator, no host wait (capturable).
+int wg_project_radii(const wg_project_args* args) {
+    if (!args || args->struct_size < sizeof(wg_project_args)) return WG_ERR_INVALID_ARGUMENT;
+    const wg_project_args& a = *args;
+    if (a.P < 0 || a.width <= 0 || a.height <= 0) return WG_ERR_INVALID_ARGUMENT;
+    const bool pair = a.scales != nullptr && a.rotations != nullptr, half_pair = (a.scales != nullptr) != (a.rotations != nullptr);
+    if (a.P > 0) {
+        if (!a.means3D || !a.viewmatrix || !a.projmatrix || !a.radii) return WG_ERR_INVALID_ARGUMENT;
+        if (half_pair || pair == (a.cov3D_precomp != nullptr)) return WG_ERR_INVALID_ARGUMENT;   // both or neither covariance source
+    }
+    if (a.filter_3D != nullptr && (a.cov3D_precomp != nullptr || (a.P > 0 && !pair))) return WG_ERR_INVALID_ARGUMENT;   // raw parameters are scale / rotation pairs
+    if (a.P == 0) return WG_OK;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(a.stream);
+    wg::ProjectParams pp;
+    pp.P = a.P; pp.W = a.width; pp.H = a.height;
+    pp.gx = (a.width + wg::TILE_X - 1) / wg::TILE_X; pp.gy = (a.height + wg::TILE_Y - 1) / wg::TILE_Y;
+    pp.means3D = a.means3D; pp.scales = a.scales; pp.rotations = a.rotations; pp.cov3D_precomp = a.cov3D_precomp; pp.filter_3D = a.filter_3D;
+    pp.viewmatrix = a.viewmatrix; pp.projmatrix = a.projmatrix;
+    pp.scale_modifier = a.scale_modifier; pp.tan_fovx = a.tan_fovx; pp.tan_fovy = a.tan_fovy;
+    pp.focal_y = a.height / (2.0f * a.tan_fovy);   // forward_params' expressions: the same focal lengths
+    pp.focal_x = a.width / (2.0f * a.tan_fovx);
+    pp.kernel_size = a.kernel_size;
+    pp.rot_vec = reinterpret_cast<uintptr_t>(a.rotations) % 16 == 0;
+    pp.radii = a.radii;
+    const bool marked = g_roctx.enabled;
+    if (marked) g_roctx.push("wg:project_radii");
+    const hipError_t e = wg::launch_project_radii(pp, stream);
+    if (marked) g_roctx.pop();
+    if (e != hipSuccess) return hip_fail(e, "project_radii");
+    return WG_OK;
+}
+
 int wg_view_geometry(char* geom_buffer, int P, wg_geometry_view* out) {
     if (!geom_buffer || !out || P < 0) return WG_ERR_INVALID_ARGUMENT;
     wg::GeometryState g = wg::GeometryState::fromChunk(geom_buffer, (size_t)P, false);

@@ -363,6 +363,59 @@ torch::Tensor markVisible(torch::Tensor& means3D, torch::Tensor& viewmatrix, tor
     return present;
 }
 
+// The projection-only pass (wg_project_radii): radii of the frame a forward call with these geometry inputs and this camera would render, from
+// one launch on torch's current stream.  The checks of _C.py's _check_project_arguments, in its order, with its messages: shapes, modes and
+// dtypes first, the device last.
+torch::Tensor ProjectRadii(const torch::Tensor& means3D, const OptTensor& scales, const OptTensor& rotations, const OptTensor& cov3D_precomp,
+                           const OptTensor& filter_3D, const float scale_modifier, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix,
+                           const float tan_fovx, const float tan_fovy, const float kernel_size, const int image_height, const int image_width) {
+    if (means3D.ndimension() != 2 || means3D.size(1) != 3) throw std::runtime_error("means3D must have dimensions (num_points, 3)");
+    const int64_t P64 = means3D.size(0);
+    if (scales.has_value() != rotations.has_value() || scales.has_value() == cov3D_precomp.has_value())
+        throw std::runtime_error("project_radii needs exactly one of a scales / rotations pair or cov3D_precomp");
+    if (filter_3D.has_value() && (cov3D_precomp.has_value() || filter_3D->numel() != P64))
+        throw std::runtime_error("filter_3D (raw-parameter mode) needs scales and rotations, and P filter values");
+    const std::pair<const char*, const torch::Tensor*> named[] = {
+        {"means3D", &means3D}, {"scales", opt(scales)}, {"rotations", opt(rotations)}, {"cov3D_precomp", opt(cov3D_precomp)},
+        {"filter_3D", opt(filter_3D)}, {"viewmatrix", &viewmatrix}, {"projmatrix", &projmatrix}};
+    for (const auto& n : named)
+        if (n.second && n.second->scalar_type() != torch::kFloat32) throw std::runtime_error(std::string(n.first) + " must be float32");
+    auto sized = [&](const OptTensor& t, int64_t per, const char* name) {
+        if (t.has_value() && t->numel() != per * P64) throw std::runtime_error(std::string(name) + " must have " + std::to_string(per) + " * P elements");
+    };
+    sized(scales, 3, "scales"); sized(rotations, 4, "rotations"); sized(cov3D_precomp, 6, "cov3D_precomp");
+    for (const auto& n : {named[5], named[6]})
+        if (n.second->ndimension() != 2 || n.second->size(0) != 4 || n.second->size(1) != 4)
+            throw std::runtime_error(std::string(n.first) + " must have dimensions (4, 4)");
+    if (image_height <= 0 || image_width <= 0) throw std::runtime_error("image_height and image_width must be positive");
+    for (const auto& n : named)
+        if (n.second && (!n.second->is_cuda() || n.second->device() != means3D.device()))
+            throw std::runtime_error(std::string(n.first) + " must live on a HIP device, the one of means3D: this pass has no CPU path");
+
+    const auto dev = means3D.device();
+    const c10::DeviceGuard guard(dev);
+    torch::Tensor radii = torch::empty({P64}, means3D.options().dtype(torch::kInt32));   // fully written by the kernel
+    if (P64 == 0) return radii;
+    auto cont = [](const OptTensor& t) { return t.has_value() ? t->contiguous() : torch::Tensor(); };
+    const auto m3 = means3D.contiguous(), sc = cont(scales), rot = cont(rotations), cov = cont(cov3D_precomp), f3d = cont(filter_3D),
+               vm = viewmatrix.contiguous(), pm = projmatrix.contiguous();
+    wg_project_args a{};
+    a.struct_size = sizeof(a);
+    a.P = static_cast<int>(P64); a.width = image_width; a.height = image_height;
+    a.means3D = ptr(m3); a.scales = ptr(sc); a.rotations = ptr(rot); a.cov3D_precomp = ptr(cov); a.filter_3D = ptr(f3d);
+    a.scale_modifier = scale_modifier; a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy; a.kernel_size = kernel_size;
+    a.viewmatrix = ptr(vm); a.projmatrix = ptr(pm);
+    a.radii = radii.data_ptr<int>();
+    a.stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
+    int status;
+    {
+        py::gil_scoped_release nogil;
+        status = wg_project_radii(&a);
+    }
+    check(status, "wg_project_radii");
+    return radii;
+}
+
 // ---- everything beyond the reference, by argument (the blocks of wg_forward_args / wg_backward_args) -------------------------------------
 // -> the reference's six, + the second image with colors2 / sh_second
 py::tuple RasterizeGaussiansEx(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors, const torch::Tensor& opacity,
@@ -452,6 +505,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {   // ext.cpp:15-19
     m.def("rasterize_gaussians", &RasterizeGaussiansHIP);
     m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackwardHIP);
     m.def("mark_visible", &markVisible);
+    m.def("project_radii", &ProjectRadii);                                     // wg_project_radii: a frame's radii before it is rendered
     m.def("rasterize_gaussians_ex", &RasterizeGaussiansEx);                    // + the blocks of wg_forward_args, + the forward_only hint
     m.def("rasterize_gaussians_ex", &RasterizeGaussiansExNoHint);              //   (overload without the hint)
     m.def("rasterize_gaussians_backward_ex", &RasterizeGaussiansBackwardEx);   // + the blocks of wg_backward_args, + which of dL_dcolors / dL_dcov3D the caller wants

@@ -334,6 +334,21 @@ hipError_t launch_preprocess(const FwdParams& p, const ShTone& tone, const Geome
 struct SplitState;
 hipError_t launch_sh_colour(const FwdParams& p, const GeometryState& g, const SplitState* split, bool far, bool row, hipStream_t stream);
 hipError_t launch_mark_visible(int P, const float* means3D, const float* viewmatrix, unsigned char* present, hipStream_t stream);
+// the projection-only pass (project/project.hip, wg_project_radii): radii[0 .. P) with the forward call's bits, nothing else read or written
+struct ProjectParams {
+    int P, W, H, gx, gy;
+    const float* means3D;
+    const float* scales;          // with rotations, or
+    const float* rotations;
+    const float* cov3D_precomp;   // the six floats per Gaussian
+    const float* filter_3D;       // non-null: scales / rotations are the caller's RAW parameters (wg_act.h)
+    const float* viewmatrix;
+    const float* projmatrix;
+    float scale_modifier, tan_fovx, tan_fovy, focal_x, focal_y, kernel_size;
+    int rot_vec;                  // rotations is 16-byte aligned: one 16-byte load per Gaussian
+    int* radii;
+};
+hipError_t launch_project_radii(const ProjectParams& p, hipStream_t stream);
 hipError_t launch_recolor(int P, const GeometryState& src, const GeometryState& dst, const float* colors, int* radii_out, hipStream_t stream);
 hipError_t run_scan(const GeometryState& g, int P, hipStream_t stream);
 hipError_t launch_scan_overflow_check(const GeometryState& g, int P, uint32_t* flag, hipStream_t stream);  // *flag = 1: the 32-bit scan wrapped

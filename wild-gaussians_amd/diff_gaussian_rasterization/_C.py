@@ -64,7 +64,7 @@ def binding_name() -> str:
 
 
 from ._abi import (_ALLOC_FN, _vp, _i, _f, _ShTone, _SecondImage, _RawGaussians, _RecolorParent, _CallOptions, _ForwardArgs,  # noqa: E402
-                    _BackwardArgs)   # (pure ctypes)
+                    _BackwardArgs, _ProjectArgs)   # (pure ctypes)
 
 _lib.wg_rasterize_forward.restype = _i
 _lib.wg_rasterize_forward.argtypes = [_ALLOC_FN, _vp, _ALLOC_FN, _vp, _ALLOC_FN, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp,
@@ -80,6 +80,8 @@ _lib.wg_forward_status.restype = _i
 _lib.wg_forward_status.argtypes = [_vp, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]
 _lib.wg_mark_visible.restype = _i
 _lib.wg_mark_visible.argtypes = [_i, _vp, _vp, _vp, _vp, _vp]
+_lib.wg_project_radii.restype = _i
+_lib.wg_project_radii.argtypes = [C.POINTER(_ProjectArgs)]
 for _name in ("wg_geometry_buffer_size", "wg_geometry_buffer_size_rows", "wg_binning_buffer_size"):
     getattr(_lib, _name).restype = C.c_size_t
     getattr(_lib, _name).argtypes = [_i]
@@ -733,6 +735,60 @@ def mark_visible(means3D, viewmatrix, projmatrix):
             _check(_lib.wg_mark_visible(P, _ptr(means3D), _ptr(viewmatrix), _ptr(projmatrix), present.data_ptr(),
                                         _stream(device)), "wg_mark_visible")
     return present
+
+
+# ----------------------------------------------------------------------------------------------------------
+# The projection-only pass (wg_project_radii): a frame's radii -- the forward call's bits -- before it is rendered.
+def _check_project_arguments(means3D, scales, rotations, cov3D_precomp, filter_3D, viewmatrix, projmatrix, image_height, image_width):
+    """What project_radii refuses (None = not given).  Shapes, modes and dtypes first -- pure functions of the tensors' metadata --, the
+    device last.  The compiled binding makes the same checks in the same order with the same messages (csrc/torch_binding.cpp)."""
+    if means3D.dim() != 2 or means3D.size(1) != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    P = means3D.size(0)
+    if (scales is None) != (rotations is None) or (scales is None) == (cov3D_precomp is None):
+        raise RuntimeError("project_radii needs exactly one of a scales / rotations pair or cov3D_precomp")
+    if filter_3D is not None and (cov3D_precomp is not None or filter_3D.numel() != P):
+        raise RuntimeError("filter_3D (raw-parameter mode) needs scales and rotations, and P filter values")
+    named = (("means3D", means3D), ("scales", scales), ("rotations", rotations), ("cov3D_precomp", cov3D_precomp), ("filter_3D", filter_3D),
+             ("viewmatrix", viewmatrix), ("projmatrix", projmatrix))
+    for name, t in named:
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError(f"{name} must be float32")
+    for t, per, name in ((scales, 3, "scales"), (rotations, 4, "rotations"), (cov3D_precomp, 6, "cov3D_precomp")):
+        if t is not None and t.numel() != per * P:
+            raise RuntimeError(f"{name} must have {per} * P elements")
+    for name, t in (("viewmatrix", viewmatrix), ("projmatrix", projmatrix)):
+        if t.dim() != 2 or t.size(0) != 4 or t.size(1) != 4:
+            raise RuntimeError(f"{name} must have dimensions (4, 4)")
+    if int(image_height) <= 0 or int(image_width) <= 0:
+        raise RuntimeError("image_height and image_width must be positive")
+    for name, t in named:
+        if t is not None and (not t.is_cuda or t.device != means3D.device):
+            raise RuntimeError(f"{name} must live on a HIP device, the one of means3D: this pass has no CPU path")
+
+
+def project_radii(means3D, scales, rotations, cov3D_precomp, filter_3D, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy, kernel_size,
+                  image_height, image_width):
+    """radii (int32 [P]) of the frame a forward call with these geometry inputs and this camera would render -- the same bits -- from one
+    launch on torch's current stream: no colours, no scratch buffers, no host synchronisation (wg_project_radii).  `scales` + `rotations` or
+    `cov3D_precomp`, the other(s) None; with `filter_3D` the pair is the caller's RAW parameters.  float32 tensors on one HIP device."""
+    if _torch_ext is not None:
+        return _torch_ext.project_radii(means3D, scales, rotations, cov3D_precomp, filter_3D, float(scale_modifier), viewmatrix, projmatrix,
+                                        float(tan_fovx), float(tan_fovy), float(kernel_size), int(image_height), int(image_width))
+    _check_project_arguments(means3D, scales, rotations, cov3D_precomp, filter_3D, viewmatrix, projmatrix, image_height, image_width)
+    device, P = means3D.device, means3D.size(0)
+    radii = torch.empty((P,), dtype=torch.int32, device=device)   # fully written by the kernel
+    if P != 0:
+        keep = [None if t is None else t.contiguous() for t in (means3D, scales, rotations, cov3D_precomp, filter_3D, viewmatrix, projmatrix)]
+        a = _ProjectArgs()
+        a.struct_size = C.sizeof(a)
+        a.P, a.width, a.height = P, int(image_width), int(image_height)
+        a.means3D, a.scales, a.rotations, a.cov3D_precomp, a.filter_3D, a.viewmatrix, a.projmatrix = (None if t is None else t.data_ptr() for t in keep)
+        a.scale_modifier, a.tan_fovx, a.tan_fovy, a.kernel_size = float(scale_modifier), float(tan_fovx), float(tan_fovy), float(kernel_size)
+        a.radii, a.stream = radii.data_ptr(), _stream(device)
+        with torch.cuda.device(device):
+            _check(_lib.wg_project_radii(C.byref(a)), "wg_project_radii")
+    return radii
 
 
 # ----------------------------------------------------------------------------------------------------------

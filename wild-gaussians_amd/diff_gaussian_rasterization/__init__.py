@@ -214,6 +214,28 @@ class GaussianRasterizer(nn.Module):
         with torch.no_grad():
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
+    def project_radii(self, means3D, scales: Optional[torch.Tensor] = None, rotations: Optional[torch.Tensor] = None,
+                      cov3D_precomp: Optional[torch.Tensor] = None, *, filter_3D: Optional[torch.Tensor] = None,
+                      opacities: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The projection-only pass (beyond the reference): `radii` (int32 [P]) of the frame `forward` would render from these geometry inputs
+        through this rasterizer's camera -- the same bits, so `radii > 0` is the frame's visible set -- WITHOUT rendering it: one launch that
+        reads the geometry and writes 4 bytes per Gaussian; no colours, no binning, no scratch buffers, no host synchronisation.  Camera, image
+        size, `kernel_size` and `scale_modifier` come from `raster_settings`, as in `forward`.  For whatever needs a frame's visible set before
+        it has colours (`wg_fused_gaussians.VisibleRows.from_camera`: the appearance MLP over visible rows in front of ONE two-tone call).
+        `markVisible` is not this: it is the near-plane test alone and keeps everything in front of the camera, on screen or not.
+
+        `filter_3D=`: `scales` / `rotations` are the caller's RAW parameters, as in `forward(filter_3D=)`.  `opacities=` is accepted so that
+        the call can carry `forward`'s geometry arguments, and is not read: no radius depends on an opacity, raw or activated.
+        float32 tensors on one HIP device; runs under `torch.no_grad()`."""
+        has_scale_rot = scales is not None or rotations is not None
+        complete_scale_rot = scales is not None and rotations is not None
+        if (cov3D_precomp is None and not complete_scale_rot) or (cov3D_precomp is not None and has_scale_rot):
+            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+        rs = self.raster_settings
+        with torch.no_grad():
+            return _C.project_radii(means3D, scales, rotations, cov3D_precomp, filter_3D, rs.scale_modifier, rs.viewmatrix, rs.projmatrix,
+                                    rs.tanfovx, rs.tanfovy, rs.kernel_size, rs.image_height, rs.image_width)
+
     def forward(self, means3D, means2D, opacities, shs: Optional[torch.Tensor] = None,
                 colors_precomp: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None,
                 rotations: Optional[torch.Tensor] = None, cov3D_precomp: Optional[torch.Tensor] = None, *,

@@ -46,3 +46,10 @@ class _BackwardArgs(C.Structure):  # wg_backward_args
                                     "dL_dconic", "dL_dopacity", "dL_dcolor", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot", "stream")] +
                 [("tone", C.POINTER(_ShTone)), ("tone2", C.POINTER(_ShTone)), ("sh_second", _i), ("second", C.POINTER(_SecondImage)),
                  ("raw", C.POINTER(_RawGaussians)), ("options", C.POINTER(_CallOptions)), ("colour_gradients_only", _i)])
+
+
+class _ProjectArgs(C.Structure):  # wg_project_args
+    _fields_ = ([("struct_size", C.c_size_t)] + [(n, _i) for n in ("P", "width", "height")] +
+                [(n, _vp) for n in ("means3D", "scales", "rotations", "cov3D_precomp", "filter_3D")] +
+                [(n, _f) for n in ("scale_modifier", "tan_fovx", "tan_fovy", "kernel_size")] +
+                [(n, _vp) for n in ("viewmatrix", "projmatrix", "radii", "stream")])

@@ -47,6 +47,7 @@ The same operator over the rows that reach the image only, forward and backward,
 
     from wg_fused_gaussians import VisibleRows, appearance_rows
     rows = VisibleRows.from_radii(radii)                      # or .from_mask(mask) / .from_index(index)
+    rows = VisibleRows.from_camera(rasterizer, xyz, scales, rotations)   # the same list BEFORE the frame is rendered (projection-only pass)
     offset_mul = appearance_mlp((features[..., :3], gembedding), weights, shared=aembedding, rows=rows)             # [P, 6], zeros at unlisted rows
     with appearance_rows(rows): ...                           # the forward that apply_optins(appearance_mlp=True) swaps in uses the list
 
@@ -720,13 +721,15 @@ class VisibleRows:
     """The rows `appearance_mlp(rows=)` evaluates: `index` (int32 on the device), `M` (a host number: the exact entry count, or the
     capacity when `count` is given), `count` (None, or one int32 on the device: the real count) and `P` (the row count of the tensors the
     list belongs to; None when unknown).  `from_radii` and `from_mask` build the list on the device in ascending order with NO host
-    synchronisation (include/wg_appearance_rows.h): the count stays on the device and M is the capacity P."""
-    __slots__ = ("index", "M", "count", "P")
+    synchronisation (include/wg_appearance_rows.h): the count stays on the device and M is the capacity P.  `from_camera` computes the
+    radii itself, before the frame is rendered, and keeps them in `radii` (None in every other list)."""
+    __slots__ = ("index", "M", "count", "P", "radii")
 
     def __init__(self, index, M, count=None, P=None):
         if index.numel() == 0:   # the C-ABI refuses a null list; an empty one still has an address
             index = torch.zeros(1, dtype=torch.int32, device=index.device)
         self.index, self.M, self.count, self.P = index, int(M), count, (None if P is None else int(P))
+        self.radii = None
 
     @staticmethod
     def _compact(flags, is_radii):
@@ -749,6 +752,19 @@ class VisibleRows:
         if not (torch.is_tensor(radii) and radii.is_cuda and radii.dtype == torch.int32 and radii.dim() == 1):
             raise RuntimeError("wg_fused_gaussians.VisibleRows.from_radii: radii must be a 1-D int32 tensor on a HIP device")
         return cls._compact(radii.detach().contiguous(), True)
+
+    @classmethod
+    def from_camera(cls, rasterizer, means3D, scales=None, rotations=None, cov3D_precomp=None, *, filter_3D=None, opacities=None):
+        """The rows that reach the image of `rasterizer`'s camera, BEFORE the frame is rendered: the projection-only pass
+        (`GaussianRasterizer.project_radii`, same arguments: include/wg_rasterizer.h, wg_project_radii), then `from_radii`'s compaction -- four
+        launches on the current stream, no host synchronisation, the count stays on the device.  The radii are the bits the forward call will
+        write, so the list is the one `from_radii(radii_of_the_forward_call)` builds; they are kept in `.radii`.  With it the step can run the
+        appearance MLP over the visible rows only AND render the raw and the toned image in one `sh_second=True` call (INTEGRATION.md
+        section 5)."""
+        radii = rasterizer.project_radii(means3D, scales, rotations, cov3D_precomp, filter_3D=filter_3D, opacities=opacities)
+        rows = cls._compact(radii, True)
+        rows.radii = radii
+        return rows
 
     @classmethod
     def from_mask(cls, mask):
