@@ -254,7 +254,7 @@ int wg_view_image(char* image_buffer, int width, int height, wg_image_view* out)
 
 /* ---- per-stage timing with HIP events on the caller's stream (bench.py's roofline): enable, run, read (synchronises) ---- */
 enum { WG_STAGE_PREPROCESS = 0, WG_STAGE_SCAN, WG_STAGE_DUPLICATE_KEYS, WG_STAGE_SORT, WG_STAGE_TILE_RANGES,
-       WG_STAGE_RENDER_FORWARD, WG_STAGE_RENDER_BACKWARD, WG_STAGE_PREPROCESS_BACKWARD, WG_STAGE_RENDER_FIXUP, WG_STAGE_COUNT };
+       WG_STAGE_RENDER_FORWARD, WG_STAGE_RENDER_BACKWARD, WG_STAGE_PREPROCESS_BACKWARD, WG_STAGE_RENDER_FIXUP, WG_STAGE_RENDER_DEPTH, WG_STAGE_COUNT };
 typedef struct wg_stage_times {
     double total_ms[WG_STAGE_COUNT];
     long long launches[WG_STAGE_COUNT];
@@ -300,6 +300,38 @@ typedef struct wg_project_args {
     void* stream;
 } wg_project_args;
 int wg_project_radii(const wg_project_args* args);
+
+/* ---- the depth pass: one scalar per Gaussian composited over a FINISHED frame like a colour channel ----
+ *   out_depth[pixel] = sum over the (pixel, Gaussian) pairs the frame's forward call blended of  v[Gaussian] * alpha * T
+ * with the forward call's own decisions, alpha and T, and the forward kernel's multiply-add: the bits of one channel of a three-channel
+ * forward call over the same geometry with colors_precomp = v repeated and an all-zero background (what the caller's depth render,
+ * wildgaussians/method.py:1621-1631, keeps of its second rasterizer call).  No background term, no division by the accumulation.
+ *   values: float[P], the scalars; or NULL = the distance to the camera, sqrtf(dx*dx + dy*dy + dz*dz) of means3D[i] - campos (means3D float[P*3],
+ *     campos float[3], both DEVICE pointers) -- torch.norm(means3D - camera_center[None], dim=-1).  WG_ERR_INVALID_ARGUMENT when both sources
+ *     are missing; with values given, means3D / campos are not read.
+ *   geom_buffer / binning_buffer / image_buffer, R, subpixel_offset, options: the frame's, as its backward call takes them (a frame served by
+ *     a recolouring call: its NEW geometry buffer and the parent's other two).  options->exact_compositing must be the frame's
+ *     (WG_ERR_INVALID_ARGUMENT otherwise, as in the backward call); the other two options are not read.
+ * One launch on `stream` over each tile's list up to tile_last.  The three buffers are only READ: a backward call of the frame before or after
+ * it behaves as without it.  No scratch, no allocator, no atomics, no host wait -- but for a frame of the deferred forward, whose verdict is read
+ * first (WG_ERR_SPECULATION: the frame did not fit, nothing is written).  out_depth: float[H*W], fully overwritten, 0 for a pixel without a
+ * contributor; P = 0 or R = 0 zero-fill it and return WG_OK.  Two calls give the same bits.
+ * WG_ERR_INVALID_ARGUMENT, before any device work: struct_size smaller than the struct, P < 0, R < 0, width or height <= 0, a NULL out_depth,
+ * with P > 0 a NULL buffer or no scalar source.  Fields are only ever appended. */
+typedef struct wg_depth_args {
+    size_t struct_size;   /* the CALLER's sizeof(wg_depth_args) */
+    int P, R, width, height;
+    char *geom_buffer, *binning_buffer, *image_buffer;
+    const float* subpixel_offset;   /* the frame's float[H*W*2], or NULL */
+    const float* values;            /* [P] or NULL */
+    const float* means3D;           /* [P*3], read when values is NULL */
+    const float* campos;            /* [3], device, read when values is NULL */
+    const wg_call_options* options; /* NULL = WG_CALL_OPTIONS_DEFAULT */
+    float* out_depth;               /* [H*W], fully overwritten */
+    int debug;                      /* 1: synchronise behind the launch and report (as the other calls' debug) */
+    void* stream;
+} wg_depth_args;
+int wg_render_depth(const wg_depth_args* args);
 
 #ifdef __cplusplus
 }

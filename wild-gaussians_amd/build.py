@@ -35,6 +35,8 @@ SOURCES = {
     "project/project.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],   # the projection-only pass (wg_project_radii): preprocess.hip's
                                                                            # geometry restated under preprocess.hip's flags, so that radii has
                                                                            # the forward call's bits; in a subdirectory like the other opt-ins
+    "depth/depth.hip": ["-fno-slp-vectorize"],   # the depth pass (wg_render_depth): the forward walk over a finished frame with one per-pixel sum;
+                                                 # render_fwd.hip's flags, so that the sum has the forward kernel's instruction and its bits
     "binning.hip": ["-fno-slp-vectorize"],
     "render_fwd.hip": ["-fno-slp-vectorize"],
     "render_bwd.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],

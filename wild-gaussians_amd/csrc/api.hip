@@ -314,7 +314,7 @@ struct StageScope {
 const char* stage_label(int stage) {
     static const char* names[WG_STAGE_COUNT] = {"wg:K1 preprocess", "wg:K2-K3 scan", "wg:K4 duplicate_keys", "wg:K5 sort", "wg:K6-K7 tile_ranges",
                                                 "wg:K8 render_forward", "wg:K9 render_backward", "wg:K10-K11 preprocess_backward",
-                                                "wg:K8 render_fixup"};
+                                                "wg:K8 render_fixup", "wg:K8d render_depth"};
     return (stage >= 0 && stage < WG_STAGE_COUNT) ? names[stage] : "wg:?";
 }
 
@@ -1405,6 +1405,42 @@ int wg_project_radii(const wg_project_args* args) {
     return WG_OK;
 }
 
+// The depth pass (depth/depth.hip: render_depth_kernel): one launch over the finished frame's lists, modelled on backward_colour_impl above.  The
+// frame's three buffers are only read: no order array, no gradient record, no clean mark, no per-thread history is touched, so a backward call
+// of the frame behaves as without it.
+int wg_render_depth(const wg_depth_args* args) {
+    if (!args || args->struct_size < sizeof(wg_depth_args)) return WG_ERR_INVALID_ARGUMENT;
+    const wg_depth_args& a = *args;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(a.stream);
+    const int P = a.P, R = a.R, width = a.width, height = a.height, debug = a.debug;
+    const wg::Options opt = call_options_snapshot(a.options);
+    if (a.image_buffer != nullptr && P > 0) {   // the frame was composited with the other arithmetic: its stored decisions are not this call's
+        const int fwd_mode = remembered_mode(a.image_buffer);
+        if (fwd_mode >= 0 && fwd_mode != (opt.exact_compositing ? 1 : 0)) return WG_ERR_INVALID_ARGUMENT;
+    }
+    if (P < 0 || R < 0 || width <= 0 || height <= 0 || !a.out_depth) return WG_ERR_INVALID_ARGUMENT;
+    if (P > 0 && (!a.geom_buffer || !a.binning_buffer || !a.image_buffer)) return WG_ERR_INVALID_ARGUMENT;
+    if (P > 0 && !a.values && !(a.means3D && a.campos)) return WG_ERR_INVALID_ARGUMENT;   // no scalar source
+    if (a.image_buffer != nullptr) {   // a deferred forward call's verdict, as in the backward passes
+        const int verdict = check_ticket(image_key(a.image_buffer), stream);
+        if (verdict != WG_OK) return verdict;
+    }
+    if (P == 0 || R == 0) {   // no lists to walk: every pixel is without a contributor
+        StageScope scope_(WG_STAGE_RENDER_DEPTH, stream);
+        hipError_t e = hipMemsetAsync(a.out_depth, 0, (size_t)width * height * sizeof(float), stream);
+        if (e != hipSuccess) return hip_fail(e, "depth memset");
+        return WG_OK;
+    }
+    const int gx = (width + wg::TILE_X - 1) / wg::TILE_X, gy = (height + wg::TILE_Y - 1) / wg::TILE_Y;
+    char *geom_buffer = a.geom_buffer, *binning_buffer = a.binning_buffer, *image_buffer = a.image_buffer;   // (fromChunk advances its argument)
+    wg::GeometryState geom = wg::GeometryState::fromChunk(geom_buffer, (size_t)P, false);
+    wg::BinningState bin = wg::BinningState::fromChunk(binning_buffer, (size_t)R, false);  // only point_list is used
+    wg::ImageState img = wg::ImageState::fromChunk(image_buffer, (size_t)width * height, (size_t)gx * gy);
+    WG_STAGE(WG_STAGE_RENDER_DEPTH, wg::launch_render_depth(width, height, gx, gy, img, bin, geom, a.subpixel_offset, a.values, a.means3D, a.campos,
+                                                            a.out_depth, opt.exact_compositing != 0, stream), "render_depth");
+    return WG_OK;
+}
+
 int wg_view_geometry(char* geom_buffer, int P, wg_geometry_view* out) {
     if (!geom_buffer || !out || P < 0) return WG_ERR_INVALID_ARGUMENT;
     wg::GeometryState g = wg::GeometryState::fromChunk(geom_buffer, (size_t)P, false);
@@ -1582,7 +1618,7 @@ int wg_profile_read(wg_stage_times* out) {
 
 const char* wg_stage_name(int stage) {
     static const char* names[WG_STAGE_COUNT] = {"preprocess", "scan", "duplicate_keys", "sort", "tile_ranges",
-                                                "render_forward", "render_backward", "preprocess_backward", "render_fixup"};
+                                                "render_forward", "render_backward", "preprocess_backward", "render_fixup", "render_depth"};
     return (stage >= 0 && stage < WG_STAGE_COUNT) ? names[stage] : "?";
 }
 

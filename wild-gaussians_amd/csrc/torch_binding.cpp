@@ -416,6 +416,65 @@ torch::Tensor ProjectRadii(const torch::Tensor& means3D, const OptTensor& scales
     return radii;
 }
 
+// The depth pass (wg_render_depth): one scalar per Gaussian composited over the finished frame these three buffers belong to -> depth [H, W].
+// The checks of _C.py's _check_depth_arguments, in its order, with its messages.
+torch::Tensor RenderDepth(const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const int R, const int P,
+                          const int image_height, const int image_width, const py::object& source, const OptTensor& means3D, const OptTensor& campos,
+                          const OptTensor& subpixel_offset, const std::tuple<int, int, int>& options, const OptTensor& out, const bool debug) {
+    const char* source_msg = "return_depth must be \"distance\" or a float32 [P] tensor of per-Gaussian scalars on the frame's HIP device";
+    const auto dev = imageBuffer.device();
+    const bool distance = py::isinstance<py::str>(source);
+    torch::Tensor values;
+    if (distance) {
+        if (source.cast<std::string>() != "distance") throw std::runtime_error(source_msg);
+    } else {
+        if (!THPVariable_Check(source.ptr())) throw std::runtime_error(source_msg);
+        values = source.cast<torch::Tensor>();
+        if (values.scalar_type() != torch::kFloat32) throw std::runtime_error(source_msg);
+        if (values.numel() != P) throw std::runtime_error("depth values must have P elements");
+        if (!values.is_cuda() || values.device() != dev) throw std::runtime_error(source_msg);
+    }
+    if (distance) {
+        if (!means3D.has_value() || !campos.has_value()) throw std::runtime_error("depth source \"distance\" needs means3D and campos");
+        if (means3D->scalar_type() != torch::kFloat32 || means3D->numel() != 3 * (int64_t)P || campos->scalar_type() != torch::kFloat32 || campos->numel() != 3)
+            throw std::runtime_error("means3D must be float32 with 3 * P elements, campos float32 with 3");
+        if (!means3D->is_cuda() || means3D->device() != dev || !campos->is_cuda() || campos->device() != dev)
+            throw std::runtime_error("means3D and campos must live on the frame's HIP device");
+    }
+    if (P < 0 || R < 0 || image_height <= 0 || image_width <= 0)
+        throw std::runtime_error("P and num_rendered must not be negative, image_height and image_width must be positive");
+    const int64_t N = (int64_t)image_height * image_width;
+    if (subpixel_offset.has_value() && subpixel_offset->numel() != 0 &&
+        (subpixel_offset->scalar_type() != torch::kFloat32 || subpixel_offset->numel() != 2 * N || subpixel_offset->device() != dev))
+        throw std::runtime_error("subpixel_offset must be float32 with H * W * 2 elements on the frame's HIP device");
+    if (out.has_value() && (out->scalar_type() != torch::kFloat32 || out->numel() != N || !out->is_contiguous() || out->device() != dev))
+        throw std::runtime_error("out must be a contiguous float32 tensor of H * W elements on the frame's HIP device");
+    if (!(geomBuffer.is_cuda() && binningBuffer.is_cuda() && imageBuffer.is_cuda())) throw std::runtime_error("the frame's buffers must live on a HIP device");
+
+    const c10::DeviceGuard guard(dev);
+    torch::Tensor depth = out.has_value() ? out->view({image_height, image_width})
+                                          : torch::empty({image_height, image_width}, imageBuffer.options().dtype(torch::kFloat32));   // fully written by the library
+    const auto m3 = distance ? means3D->contiguous() : torch::Tensor(), cam = distance ? campos->contiguous() : torch::Tensor(),
+               val = distance ? torch::Tensor() : values.contiguous(),
+               so = subpixel_offset.has_value() ? subpixel_offset->contiguous() : torch::Tensor();
+    const wg_call_options co = call_options(options);
+    wg_depth_args a{};
+    a.struct_size = sizeof(a);
+    a.P = P; a.R = R; a.width = image_width; a.height = image_height; a.debug = debug;
+    if (P != 0) { a.geom_buffer = bytes_of(geomBuffer); a.binning_buffer = bytes_of(binningBuffer); a.image_buffer = bytes_of(imageBuffer); }
+    a.subpixel_offset = ptr(so); a.values = ptr(val); a.means3D = ptr(m3); a.campos = ptr(cam);
+    a.options = &co;
+    a.out_depth = depth.data_ptr<float>();
+    a.stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
+    int status;
+    {
+        py::gil_scoped_release nogil;
+        status = wg_render_depth(&a);
+    }
+    check(status, "wg_render_depth");
+    return depth;
+}
+
 // ---- everything beyond the reference, by argument (the blocks of wg_forward_args / wg_backward_args) -------------------------------------
 // -> the reference's six, + the second image with colors2 / sh_second
 py::tuple RasterizeGaussiansEx(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors, const torch::Tensor& opacity,
@@ -506,6 +565,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {   // ext.cpp:15-19
     m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackwardHIP);
     m.def("mark_visible", &markVisible);
     m.def("project_radii", &ProjectRadii);                                     // wg_project_radii: a frame's radii before it is rendered
+    m.def("render_depth", &RenderDepth);                                       // wg_render_depth: a scalar per Gaussian composited over a finished frame
     m.def("rasterize_gaussians_ex", &RasterizeGaussiansEx);                    // + the blocks of wg_forward_args, + the forward_only hint
     m.def("rasterize_gaussians_ex", &RasterizeGaussiansExNoHint);              //   (overload without the hint)
     m.def("rasterize_gaussians_backward_ex", &RasterizeGaussiansBackwardEx);   // + the blocks of wg_backward_args, + which of dL_dcolors / dL_dcov3D the caller wants

@@ -465,6 +465,11 @@ hipError_t launch_render_backward(int W, int H, int gx, int gy, const ImageState
 // first tile_last entries in img.order_bwd's order; dL_dcolor must arrive cleared
 hipError_t launch_render_backward_colour(int W, int H, int gx, int gy, const ImageState& img, const BinningState& b, const GeometryState& g,
                                          const float* subpixel_offset, const float* dL_dpix, float* dL_dcolor, bool exact, hipStream_t stream);
+// the depth pass (depth/depth.hip: render_depth_kernel): depth[H * W] = the forward pass's blend weights times one scalar per Gaussian --
+// values[id], or with values == nullptr |means3D[id] - campos| -- over each tile's first tile_last entries, in image order; only reads the frame
+hipError_t launch_render_depth(int W, int H, int gx, int gy, const ImageState& img, const BinningState& b, const GeometryState& g,
+                               const float* subpixel_offset, const float* values, const float* means3D, const float* campos, float* depth,
+                               bool exact, hipStream_t stream);
 
 struct BwdParams {
     int P, D, M, W, H;

@@ -64,7 +64,7 @@ def binding_name() -> str:
 
 
 from ._abi import (_ALLOC_FN, _vp, _i, _f, _ShTone, _SecondImage, _RawGaussians, _RecolorParent, _CallOptions, _ForwardArgs,  # noqa: E402
-                    _BackwardArgs, _ProjectArgs)   # (pure ctypes)
+                    _BackwardArgs, _ProjectArgs, _DepthArgs)   # (pure ctypes)
 
 _lib.wg_rasterize_forward.restype = _i
 _lib.wg_rasterize_forward.argtypes = [_ALLOC_FN, _vp, _ALLOC_FN, _vp, _ALLOC_FN, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp,
@@ -82,6 +82,8 @@ _lib.wg_mark_visible.restype = _i
 _lib.wg_mark_visible.argtypes = [_i, _vp, _vp, _vp, _vp, _vp]
 _lib.wg_project_radii.restype = _i
 _lib.wg_project_radii.argtypes = [C.POINTER(_ProjectArgs)]
+_lib.wg_render_depth.restype = _i
+_lib.wg_render_depth.argtypes = [C.POINTER(_DepthArgs)]
 for _name in ("wg_geometry_buffer_size", "wg_geometry_buffer_size_rows", "wg_binning_buffer_size"):
     getattr(_lib, _name).restype = C.c_size_t
     getattr(_lib, _name).argtypes = [_i]
@@ -792,6 +794,85 @@ def project_radii(means3D, scales, rotations, cov3D_precomp, filter_3D, scale_mo
 
 
 # ----------------------------------------------------------------------------------------------------------
+# The depth pass (wg_render_depth): one scalar per Gaussian composited over a finished frame like a colour channel.
+DEPTH_SOURCE_MSG = 'return_depth must be "distance" or a float32 [P] tensor of per-Gaussian scalars on the frame\'s HIP device'
+DEPTH_CAPACITY_MSG = ("return_depth cannot be combined with binning_capacity: a fixed-capacity frame that did not fit has no lists to walk, "
+                      "and its verdict is not known when the depth pass is queued")
+
+
+def check_depth_source(source, P=None):
+    """What `return_depth` / `source` may be, as far as no device is needed (P = None: the size is checked later).  The compiled binding makes
+    the same checks in the same order with the same messages (csrc/torch_binding.cpp: RenderDepth)."""
+    if isinstance(source, str):
+        if source != "distance":
+            raise RuntimeError(DEPTH_SOURCE_MSG)
+        return
+    if not isinstance(source, torch.Tensor) or source.dtype != torch.float32:
+        raise RuntimeError(DEPTH_SOURCE_MSG)
+    if P is not None and source.numel() != P:
+        raise RuntimeError("depth values must have P elements")
+
+
+def _check_depth_arguments(geomBuffer, binningBuffer, imageBuffer, num_rendered, P, image_height, image_width, source, means3D, campos,
+                           subpixel_offset, out):
+    """What render_depth refuses: the source first (type, dtype, size, device), then the distance mode's inputs, the frame's size, the
+    sub-pixel offsets and the output."""
+    device = imageBuffer.device
+    check_depth_source(source, P)
+    if isinstance(source, torch.Tensor):
+        if not source.is_cuda or source.device != device:
+            raise RuntimeError(DEPTH_SOURCE_MSG)
+    else:
+        if means3D is None or campos is None:
+            raise RuntimeError('depth source "distance" needs means3D and campos')
+        if means3D.dtype != torch.float32 or means3D.numel() != 3 * P or campos.dtype != torch.float32 or campos.numel() != 3:
+            raise RuntimeError("means3D must be float32 with 3 * P elements, campos float32 with 3")
+        if not means3D.is_cuda or means3D.device != device or not campos.is_cuda or campos.device != device:
+            raise RuntimeError("means3D and campos must live on the frame's HIP device")
+    if int(P) < 0 or int(num_rendered) < 0 or int(image_height) <= 0 or int(image_width) <= 0:
+        raise RuntimeError("P and num_rendered must not be negative, image_height and image_width must be positive")
+    if subpixel_offset is not None and subpixel_offset.numel() != 0 and (
+            subpixel_offset.dtype != torch.float32 or subpixel_offset.numel() != 2 * int(image_height) * int(image_width) or subpixel_offset.device != device):
+        raise RuntimeError("subpixel_offset must be float32 with H * W * 2 elements on the frame's HIP device")
+    if out is not None and (out.dtype != torch.float32 or out.numel() != int(image_height) * int(image_width) or not out.is_contiguous()
+                            or out.device != device):
+        raise RuntimeError("out must be a contiguous float32 tensor of H * W elements on the frame's HIP device")
+    if not (geomBuffer.is_cuda and binningBuffer.is_cuda and imageBuffer.is_cuda):
+        raise RuntimeError("the frame's buffers must live on a HIP device")
+
+
+def render_depth(geomBuffer, binningBuffer, imageBuffer, num_rendered, P, image_height, image_width, source, means3D=None, campos=None,
+                 subpixel_offset=None, options=None, out=None, debug=False):
+    """depth (float32 [H, W]) of the finished frame these three buffers belong to (what rasterize_gaussians returned; num_rendered = its first
+    element): sum over the pairs the frame blended of v * alpha * T, no background, no normalisation (wg_render_depth) -- one launch on torch's
+    current stream that only reads the frame.  source: "distance" (v = |means3D - campos|, both then required) or a float32 [P] device tensor.
+    subpixel_offset / options: the frame's.  out: a contiguous float32 tensor of H * W elements to write into (returned viewed as [H, W])."""
+    opts = resolve_call_options(options)
+    H, W = int(image_height), int(image_width)
+    if _torch_ext is not None:
+        return _torch_ext.render_depth(geomBuffer, binningBuffer, imageBuffer, int(num_rendered), int(P), H, W, source, means3D, campos,
+                                       subpixel_offset, opts, out, bool(debug))
+    _check_depth_arguments(geomBuffer, binningBuffer, imageBuffer, num_rendered, P, H, W, source, means3D, campos, subpixel_offset, out)
+    device = imageBuffer.device
+    depth = torch.empty((H, W), dtype=torch.float32, device=device) if out is None else out.view(H, W)   # fully written by the library
+    distance = isinstance(source, str)
+    keep = [t.contiguous() if t is not None and t.numel() != 0 else None
+            for t in ((means3D if distance else None), (campos if distance else None), (None if distance else source), subpixel_offset)]
+    a = _DepthArgs()
+    a.struct_size = C.sizeof(a)
+    a.P, a.R, a.width, a.height, a.debug = int(P), int(num_rendered), W, H, int(bool(debug))
+    if int(P) != 0:
+        a.geom_buffer, a.binning_buffer, a.image_buffer = geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr()
+    a.means3D, a.campos, a.values, a.subpixel_offset = (None if t is None else t.data_ptr() for t in keep)
+    ob = _CallOptions(*opts)
+    a.options = C.pointer(ob)
+    a.out_depth, a.stream = depth.data_ptr(), _stream(device)
+    with torch.cuda.device(device):
+        _check(_lib.wg_render_depth(C.byref(a)), "wg_render_depth")
+    return depth
+
+
+# ----------------------------------------------------------------------------------------------------------
 # Introspection for the parity tests: typed views into the opaque scratch buffers (device tensors, no copy).
 def _from_ptr(ptr, shape, dtype, owner):
     # torch.frombuffer cannot wrap device memory; the CUDA array interface can
@@ -878,7 +959,7 @@ def version() -> str:
 
 # ----------------------------------------------------------------------------------------------------------
 # Per-stage HIP-event timing (wg_profile_* in wg_rasterizer.h); used by bench.py for the roofline object.
-STAGE_COUNT = 9  # WG_STAGE_COUNT (include/wg_rasterizer.h)
+STAGE_COUNT = 10  # WG_STAGE_COUNT (include/wg_rasterizer.h)
 
 
 class _StageTimes(C.Structure):

@@ -53,3 +53,9 @@ class _ProjectArgs(C.Structure):  # wg_project_args
                 [(n, _vp) for n in ("means3D", "scales", "rotations", "cov3D_precomp", "filter_3D")] +
                 [(n, _f) for n in ("scale_modifier", "tan_fovx", "tan_fovy", "kernel_size")] +
                 [(n, _vp) for n in ("viewmatrix", "projmatrix", "radii", "stream")])
+
+
+class _DepthArgs(C.Structure):  # wg_depth_args
+    _fields_ = ([("struct_size", C.c_size_t)] + [(n, _i) for n in ("P", "R", "width", "height")] +
+                [(n, _vp) for n in ("geom_buffer", "binning_buffer", "image_buffer", "subpixel_offset", "values", "means3D", "campos")] +
+                [("options", C.POINTER(_CallOptions)), ("out_depth", _vp), ("debug", _i), ("stream", _vp)])
