@@ -210,8 +210,16 @@ typedef struct wg_backward_args {
                                           dL_dcolor, dL_dpix, background and the three buffers; every other output pointer may be NULL and is
                                           never written; the grad_record option is ignored.  WG_ERR_INVALID_ARGUMENT with shs, tone, tone2,
                                           sh_second, second, raw, or deterministic_backward = 1.  Absent (a struct of version 0.5's 312
-                                          bytes) = 0 = the full backward pass. */
+                                          bytes) = 0 = the full backward pass.
+                                          2 (WG_COLOUR_GRADIENTS_FIXED_ORDER): the same gradient without float atomics -- every (tile, Gaussian)
+                                          term is stored into a slot of the library's leased scratch (16 bytes + 1 flag byte per instance) and
+                                          a second kernel adds each Gaussian's terms in an order fixed by the frame: two calls give the same
+                                          bits.  Same needs and refusals as 1 (deterministic_backward = 1 included: that option belongs to the
+                                          full pass); additionally refused inside a stream capture, like the full pass's deterministic mode.
+                                          Any other non-zero value behaves as 1. */
 } wg_backward_args;
+#define WG_COLOUR_GRADIENTS_ATOMIC 1
+#define WG_COLOUR_GRADIENTS_FIXED_ORDER 2
 
 int wg_rasterize_forward_ex(const wg_forward_args* args);
 int wg_rasterize_backward_ex(const wg_backward_args* args);

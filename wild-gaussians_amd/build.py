@@ -40,6 +40,8 @@ SOURCES = {
     "binning.hip": ["-fno-slp-vectorize"],
     "render_fwd.hip": ["-fno-slp-vectorize"],
     "render_bwd.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],
+    "colour_bwd/fixed_order.hip": ["-fno-slp-vectorize"],   # the colour-only backward pass in a fixed summation order: K9c's walk with slot
+                                                            # stores + an ordered per-Gaussian sum; render_bwd.hip's flags less the atomics' one
     "preprocess_bwd.hip": ["-fno-slp-vectorize"],
     "api.hip": [],
     "knn.hip": ["-ffp-contract=off"],  # simple_knn.distCUDA2 replacement (include/wg_knn.h)

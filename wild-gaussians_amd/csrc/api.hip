@@ -1323,10 +1323,15 @@ static int backward_impl(const wg_backward_args& a) {
 // wg_backward_args::colour_gradients_only: dL_dcolor alone, from one front-to-back walk over the frame's lists (render_bwd.hip: render_backward_colour_kernel).
 // Called by backward_impl once the frame's exact_compositing has been matched against the call's.  Nothing is recorded (grad_record is
 // ignored), no scratch is leased, no per-Gaussian kernel follows: the call captures in a hipGraph like the atomic mode of the full pass.
+// colour_gradients_only = WG_COLOUR_GRADIENTS_FIXED_ORDER: the same sums without atomics (colour_bwd/fixed_order.hip) -- the full pass's deterministic
+// machinery for three sums: the scan of tiles_touched, a leased block of 16 bytes per instance + a flag byte each, the flags cleared by the
+// launch that orders the tiles, the walk, the ordered sum.  dL_dcolor is written in full by the ordered sum: no clear of it.  Refused inside
+// a stream capture (a replay would write into a block that was only leased for the call), before anything is launched.
 static int backward_colour_impl(const wg_backward_args& a, const wg::Options& opt) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(a.stream);
     const int P = a.P, R = a.R, width = a.width, height = a.height, debug = a.debug;
-    // SH colours, tones, a second image and raw parameters have per-Gaussian work behind dL_dcolor; a slot path for three sums does not exist
+    // SH colours, tones, a second image and raw parameters have per-Gaussian work behind dL_dcolor; deterministic_backward is the FULL pass's option
+    // (the colour-only pass's slot path is asked for through the flag's value, below) and stays refused with either value
     if (a.shs || a.tone || a.tone2 || a.sh_second || a.second || a.raw || opt.deterministic_backward) return WG_ERR_INVALID_ARGUMENT;
     if (a.image_buffer != nullptr) {   // a deferred forward call's verdict, as in the full pass
         const int verdict = check_ticket(image_key(a.image_buffer), stream);
@@ -1341,6 +1346,40 @@ static int backward_colour_impl(const wg_backward_args& a, const wg::Options& op
     wg::GeometryState geom = wg::GeometryState::fromChunk(geom_buffer, (size_t)P, false);
     wg::BinningState bin = wg::BinningState::fromChunk(binning_buffer, (size_t)R, false);  // only point_list is used
     wg::ImageState img = wg::ImageState::fromChunk(image_buffer, (size_t)width * height, (size_t)gx * gy);
+
+    const bool fixed = a.colour_gradients_only == WG_COLOUR_GRADIENTS_FIXED_ORDER && R > 0;   // (without instances: zeros, as below)
+    if (fixed) {
+        // scratch of the fixed-order mode (a leased block of the library's own: det_scratch_alloc), handed back on every way out
+        struct ColourSlots {
+            ScratchBlock* lease = nullptr;
+            hipStream_t s;
+            explicit ColourSlots(hipStream_t st) : s(st) {}
+            ~ColourSlots() { if (lease) (void)det_scratch_free(lease, s); }
+            hipError_t release() { ScratchBlock* q = lease; lease = nullptr; return q ? det_scratch_free(q, s) : hipSuccess; }
+        } guard(stream);
+        float* slots = nullptr;
+        unsigned char* flags = nullptr;
+        {
+            StageScope scope_(WG_STAGE_RENDER_BACKWARD, stream);
+            hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(stream, &capturing) == hipSuccess && capturing != hipStreamCaptureStatusNone) return WG_ERR_INVALID_ARGUMENT;
+            const size_t slot_bytes = ((size_t)R * 4 * sizeof(float) + 255) & ~(size_t)255;   // three sums in a 16-byte slot, never cleared
+            hipError_t e = wg::run_scan(geom, P, stream);   // the slot of an instance: exclusive prefix of tiles_touched + its tile's index in the rectangle
+            // (the flags: a whole number of 16-byte words behind the slots, cleared by the launch that orders the tiles)
+            if (e == hipSuccess) e = det_scratch_alloc(&guard.lease, slot_bytes + (((size_t)R + 15) & ~(size_t)15), stream);
+            if (e != hipSuccess) return hip_fail(e, "fixed-order colour backward scratch");
+            slots = static_cast<float*>(guard.lease->p);
+            flags = reinterpret_cast<unsigned char*>(slots) + slot_bytes;
+        }
+        WG_STAGE(WG_STAGE_RENDER_BACKWARD, wg::launch_tile_order(img.tile_last, nullptr, img.order_bwd, gx * gy, reinterpret_cast<float*>(flags), ((size_t)R + 3) / 4,
+                                                                 opt.backward_order_period, stream), "tile_order");
+        WG_STAGE(WG_STAGE_RENDER_BACKWARD, wg::launch_render_backward_colour_fixed(width, height, gx, gy, img, bin, geom, a.subpixel_offset, a.dL_dpix, a.dL_dcolor,
+                                                                                   opt.exact_compositing != 0, slots, flags, (size_t)R, P, stream),
+                 "render_backward_colour_fixed");
+        const hipError_t e = guard.release();
+        if (e != hipSuccess) return hip_fail(e, "fixed-order colour backward scratch release");
+        return WG_OK;
+    }
 
     // dL_dcolor is an output: cleared here.  The launch that orders the tiles clears whole float4s of a 16-byte aligned array on the side; what
     // that leaves -- the last (3 P) % 4 floats, an unaligned array, a frame without instances -- takes a memset.

@@ -208,7 +208,7 @@ struct Gradients {
 
 Gradients backward(const Scene& s, const torch::Tensor& radii, const torch::Tensor& dL_dout_color, const torch::Tensor& geomBuffer, const int R,
                    const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const py::object& sh_tone, const OptTensor& dL_dout_color2,
-                   const py::object& raw_in, const py::object& sh_second, const wg_call_options& co, const bool colour_only = false,
+                   const py::object& raw_in, const py::object& sh_second, const wg_call_options& co, const int colour_only = 0,   // (wg_backward_args::colour_gradients_only)
                    const bool want_colors = true, const bool want_cov3D = true) {
     const auto dev = s.means3D.device();
     const c10::DeviceGuard guard(dev);
@@ -253,7 +253,7 @@ Gradients backward(const Scene& s, const torch::Tensor& radii, const torch::Tens
         a.geom_buffer = bytes_of(geomBuffer); a.binning_buffer = bytes_of(binningBuffer); a.image_buffer = bytes_of(imageBuffer);
         a.dL_dpix = ptr(dL);
         a.dL_dcolor = g.colors.data_ptr<float>();
-        a.colour_gradients_only = 1;
+        a.colour_gradients_only = colour_only;   // 1: atomics; WG_COLOUR_GRADIENTS_FIXED_ORDER: slots + an ordered sum
         int status;
         {
             py::gil_scoped_release nogil;
@@ -517,7 +517,7 @@ py::tuple RasterizeGaussiansBackwardEx(const torch::Tensor& background, const to
     const Scene s{background, means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, kernel_size,
                   opt(subpixel_offset), sh, degree, campos, debug};
     const Gradients g = backward(s, radii, dL_dout_color, geomBuffer, R, binningBuffer, imageBuffer, sh_tone, dL_dout_color2, raw_in, sh_second,
-                                 call_options(options), false, want_colors, want_cov3D);
+                                 call_options(options), 0, want_colors, want_cov3D);
     py::list out;
     for (const auto& t : g.eight()) out.append(or_none(t));   // (None: dL_dcolors / dL_dcov3D that the caller did not want)
     if (!sh_second.is_none()) {
@@ -552,11 +552,12 @@ py::tuple RasterizeGaussiansBackwardColour(const torch::Tensor& background, cons
                                            const float tan_fovx, const float tan_fovy, const float kernel_size, const OptTensor& subpixel_offset,
                                            const torch::Tensor& dL_dout_color, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
                                            const torch::Tensor& geomBuffer, const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
-                                           const bool debug, const std::tuple<int, int, int>& options) {
+                                           const bool debug, const std::tuple<int, int, int>& options, const int mode) {
+    if (mode != WG_COLOUR_GRADIENTS_ATOMIC && mode != WG_COLOUR_GRADIENTS_FIXED_ORDER) throw std::runtime_error("colour-only backward: mode is 1 (atomic) or 2 (fixed order)");
     const py::object none = py::none();
     const Scene s{background, means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, kernel_size,
                   opt(subpixel_offset), sh, degree, campos, debug};
-    const Gradients g = backward(s, radii, dL_dout_color, geomBuffer, R, binningBuffer, imageBuffer, none, c10::nullopt, none, none, call_options(options), true);
+    const Gradients g = backward(s, radii, dL_dout_color, geomBuffer, R, binningBuffer, imageBuffer, none, c10::nullopt, none, none, call_options(options), mode);
     return py::make_tuple(py::none(), g.colors, py::none(), py::none(), py::none(), py::none(), py::none(), py::none());
 }
 

@@ -465,6 +465,12 @@ hipError_t launch_render_backward(int W, int H, int gx, int gy, const ImageState
 // first tile_last entries in img.order_bwd's order; dL_dcolor must arrive cleared
 hipError_t launch_render_backward_colour(int W, int H, int gx, int gy, const ImageState& img, const BinningState& b, const GeometryState& g,
                                          const float* subpixel_offset, const float* dL_dpix, float* dL_dcolor, bool exact, hipStream_t stream);
+// the same sums without atomics, in an order fixed by the frame (colour_bwd/fixed_order.hip): the walk stores each (tile, Gaussian) term into its slot
+// (slots: 4 floats per instance, never cleared; flags: one byte per slot, cleared by the caller), the reduce kernel then WRITES all 3 P floats
+// of dL_dcolor (it need not arrive cleared); g.point_offsets must hold the inclusive scan of g.tiles_touched (run_scan)
+hipError_t launch_render_backward_colour_fixed(int W, int H, int gx, int gy, const ImageState& img, const BinningState& b, const GeometryState& g,
+                                               const float* subpixel_offset, const float* dL_dpix, float* dL_dcolor, bool exact, float* slots,
+                                               unsigned char* flags, size_t slot_capacity, int P, hipStream_t stream);
 // the depth pass (depth/depth.hip: render_depth_kernel): depth[H * W] = the forward pass's blend weights times one scalar per Gaussian --
 // values[id], or with values == nullptr |means3D[id] - campos| -- over each tile's first tile_last entries, in image order; only reads the frame
 hipError_t launch_render_depth(int W, int H, int gx, int gy, const ImageState& img, const BinningState& b, const GeometryState& g,

@@ -428,16 +428,32 @@ COLOUR_ONLY_MSG = ("colour_gradients_only needs precomputed colours and nothing 
                    "(no SH colours, sh_tone, sh_second, second colour set or raw parameters) and deterministic_backward = 0")
 
 
-def resolve_colour_gradients_only(value=None) -> bool:
-    """`value` (the keyword; None = not given) over the calling thread's default."""
-    return bool(getattr(_tls, "colour_gradients_only", False) if value is None else value)
+# "fixed_order" in place of True asks for the same gradient without float atomics (wg_backward_args::colour_gradients_only =
+# WG_COLOUR_GRADIENTS_FIXED_ORDER: per-instance slots + an ordered per-Gaussian sum, bit-identical run to run).  Same calls served, same calls refused.
+COLOUR_FIXED_ORDER = "fixed_order"
+_COLOUR_MODE_ABI = {True: 1, COLOUR_FIXED_ORDER: 2}   # the C-ABI's values
+
+
+def _colour_mode(value):
+    """True / False / "fixed_order" from what a caller passed; any other string is a ValueError (checked before any device work)."""
+    if isinstance(value, str):
+        if value != COLOUR_FIXED_ORDER:
+            raise ValueError(f"colour_gradients_only is True, False, None or '{COLOUR_FIXED_ORDER}', not {value!r}")
+        return COLOUR_FIXED_ORDER
+    return bool(value)
+
+
+def resolve_colour_gradients_only(value=None):
+    """`value` (the keyword; None = not given) over the calling thread's default -> False, True or "fixed_order"."""
+    return getattr(_tls, "colour_gradients_only", False) if value is None else _colour_mode(value)
 
 
 @contextlib.contextmanager
 def colour_gradients_only(on=True):
-    """`with _C.colour_gradients_only(True): ...` -- the calling thread's default for the block."""
+    """`with _C.colour_gradients_only(True): ...` -- the calling thread's default for the block (True, False or "fixed_order")."""
+    on = _colour_mode(on)   # (an unknown string raises here, with nothing changed)
     saved = getattr(_tls, "colour_gradients_only", False)
-    _tls.colour_gradients_only = bool(on)
+    _tls.colour_gradients_only = on
     try:
         yield
     finally:
@@ -595,10 +611,10 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     options: the frame's forward call's per-call options (resolve_call_options).
     colour_gradients_only (None = the calling thread's default, off unless inside `with colour_gradients_only(True)`): only dL_dcolors [P,3]
       is computed and allocated; the eight-tuple has None in the other seven places.  Precomputed colours only, no optional block, no
-      deterministic_backward."""
+      deterministic_backward.  "fixed_order": the same without float atomics, bit-identical run to run (any other string: ValueError)."""
     global _reuse_epoch
+    colour_only = resolve_colour_gradients_only(colour_gradients_only)   # (first: an unknown string is a ValueError before anything else happens)
     opts = resolve_call_options(options)
-    colour_only = resolve_colour_gradients_only(colour_gradients_only)
     want_colors, want_cov3D = (True, True) if want is None else (bool(want[0]), bool(want[1]))
     _reuse_epoch += 1   # what the forward calls remembered ends here (see "Geometry reuse" above) ...
     states = _PerThread._states
@@ -624,9 +640,10 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             return _torch_ext.rasterize_gaussians_backward_colour(background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
                                                                   viewmatrix, projmatrix, float(tan_fovx), float(tan_fovy), float(kernel_size),
                                                                   subpixel_offset, dL_dout_color, sh, int(degree), campos, geomBuffer, int(R), binningBuffer,
-                                                                  imageBuffer, bool(debug), opts)
+                                                                  imageBuffer, bool(debug), opts, _COLOUR_MODE_ABI[colour_only])
         _check_backward_arguments(means3D, radii, colors, scales, rotations, cov3D_precomp, sh, dL_dout_color, None, None, None, None)
-        return _backward_colour_ctypes(background, means3D, colors, subpixel_offset, dL_dout_color, geomBuffer, R, binningBuffer, imageBuffer, debug, opts)
+        return _backward_colour_ctypes(background, means3D, colors, subpixel_offset, dL_dout_color, geomBuffer, R, binningBuffer, imageBuffer, debug, opts,
+                                       _COLOUR_MODE_ABI[colour_only])
     if _torch_ext is not None:
         return _torch_ext.rasterize_gaussians_backward_ex(background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
                                                           viewmatrix, projmatrix, float(tan_fovx), float(tan_fovy), float(kernel_size), subpixel_offset,
@@ -694,7 +711,7 @@ def _backward_ctypes(background, means3D, radii, colors, scales, rotations, scal
     return out if sh_tone is None else out + tone_grads   # (raw-parameter mode: same tuple, slots 2, 6, 7 are gradients of the raw parameters)
 
 
-def _backward_colour_ctypes(background, means3D, colors, subpixel_offset, dL_dout_color, geomBuffer, R, binningBuffer, imageBuffer, debug, opts):
+def _backward_colour_ctypes(background, means3D, colors, subpixel_offset, dL_dout_color, geomBuffer, R, binningBuffer, imageBuffer, debug, opts, mode=1):
     """The checked colour-only backward call through ctypes -> the reference's eight places, dL_dcolors alone filled."""
     device, P, H, W = means3D.device, means3D.size(0), dL_dout_color.size(1), dL_dout_color.size(2)
     dL_dcolors = (torch.empty if P != 0 else torch.zeros)((P, 3), dtype=torch.float32, device=device)   # the library fills it
@@ -703,7 +720,7 @@ def _backward_colour_ctypes(background, means3D, colors, subpixel_offset, dL_dou
         a = _BackwardArgs()
         _fill(a, device, P, 0, 0, H, W, debug, 1.0, 1.0, 1.0, 0.0, background=background, colors_precomp=colors, subpixel_offset=subpixel_offset,
               dL_dpix=dL_dout_color, geom_buffer=geomBuffer, binning_buffer=binningBuffer, image_buffer=imageBuffer, dL_dcolor=dL_dcolors)
-        a.R, a.colour_gradients_only = int(R), 1
+        a.R, a.colour_gradients_only = int(R), int(mode)   # 1: atomics; 2: fixed order
         keep = _attach_blocks(a, opts)  # noqa: F841  (alive until the call has returned)
         with torch.cuda.device(device):
             status = _lib.wg_rasterize_backward_ex(C.byref(a))

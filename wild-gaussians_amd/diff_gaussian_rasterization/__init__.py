@@ -27,6 +27,7 @@ from . import _C
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians"]
 call_options = _C.call_options   # `with call_options(deterministic_backward=1): ...` (thread-local, scoped; see _C.py)
 colour_gradients_only = _C.colour_gradients_only   # `with colour_gradients_only(True): ...`: the colour-only backward pass as the thread's default
+                                                   # (`"fixed_order"` in place of True: without float atomics, bit-identical run to run)
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -213,6 +214,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                         sh_mul=None, sh_offset=None, sh_pre_clamp_max=None, sh_post_clamp_max=None, binning_capacity=None, colors_precomp2=None,
                         filter_3D=None, sh_second=False, sh_mul2=None, sh_offset2=None, sh_pre_clamp_max2=None, sh_post_clamp_max2=None, call_options=None,
                         *, colour_gradients_only=None, return_depth=None):
+    _C._colour_mode(colour_gradients_only)   # (an unknown string: ValueError, before anything touches the device)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                      raster_settings, sh_mul, sh_offset, sh_pre_clamp_max, sh_post_clamp_max, binning_capacity, colors_precomp2,
                                      filter_3D, sh_second, sh_mul2, sh_offset2, sh_pre_clamp_max2, sh_post_clamp_max2, call_options,
@@ -262,7 +264,7 @@ class GaussianRasterizer(nn.Module):
                 sh_offset2: Optional[torch.Tensor] = None, sh_pre_clamp_max2: Optional[float] = None,
                 sh_post_clamp_max2: Optional[float] = None, exact_compositing: Optional[bool] = None,
                 deterministic_backward: Optional[bool] = None, grad_record: Optional[bool] = None,
-                colour_gradients_only: Optional[bool] = None, return_depth=None):
+                colour_gradients_only=None, return_depth=None):
         """`return_depth=` (keyword-only, beyond the reference): `"distance"` or a float32 [P] device tensor of per-Gaussian scalars.  The call
         then returns what it returns otherwise PLUS, as its LAST output, `depth` ([H, W] float32): the scalar composited over the frame just
         rendered like a colour channel -- sum over the blended (pixel, Gaussian) pairs of v * alpha * T, with the frame's own decisions, no
@@ -280,6 +282,10 @@ class GaussianRasterizer(nn.Module):
         optimised (WildGaussians.optimize_embedding, method.py:1755-1830).  None = the calling thread's default
         (`with colour_gradients_only(True): ...`).  Refused with `shs`, `sh_mul` / `sh_offset` / clamps, `colors_precomp2`, `filter_3D`,
         `sh_second` and `deterministic_backward=1`.
+        `colour_gradients_only="fixed_order"`: the same gradient, the same calls served and refused, WITHOUT float atomics -- every (tile,
+        Gaussian) term goes to a slot of the library's leased scratch (17 bytes per instance) and a second kernel adds each Gaussian's terms
+        in an order fixed by the frame, so two runs give the same bits (for reproducible test-time embedding fits).  Any other string raises
+        ValueError.  Not capturable in a hipGraph (the scratch is leased per call).
 
         `exact_compositing=` / `deterministic_backward=` / `grad_record=` (keyword-only, beyond the reference): the three switches that affect
         results, PER CALL (wg_call_options, include/wg_rasterizer.h); None = the calling thread's default (`_C.call_options(...)` sets it for a
@@ -311,6 +317,7 @@ class GaussianRasterizer(nn.Module):
         sh_post_clamp_max)` instead of `shs` -- WildGaussians' appearance toning (method.py:890-900, 1590-1595: pass the clamped
         features' raw tensor, `mul`, `offset / C0`, and 1.0 for both clamps) without the P x 48 intermediate tensors -- and return
         gradients for `shs` (raw), `sh_mul` and `sh_offset` ([P, 3] each)."""
+        _C._colour_mode(colour_gradients_only)   # (an unknown string: ValueError, before anything touches the device)
         if (shs is None) == (colors_precomp is None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if colors_precomp2 is not None and colors_precomp is None:

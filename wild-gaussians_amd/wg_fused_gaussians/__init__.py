@@ -1120,7 +1120,7 @@ class _ScaleGrad(torch.autograd.Function):   # the caller's scale_grads: the val
 
 def fit_appearance_embedding(rasterizer, means3D, opacities, scales, rotations, features, gembedding, weights, embedding0, gt_image, *,
                              campos=None, deg=None, iters=128, lr=0.1, loss="dssim+l1", lambda_dssim=0.2, grad_scale=None,
-                             pre_clamp_max=1.0, post_clamp_max=1.0, max_workgroups=0):
+                             pre_clamp_max=1.0, post_clamp_max=1.0, max_workgroups=0, fixed_order=False):
     """The loop of WildGaussians.optimize_embedding (wildgaussians/method.py:1786-1815) at tensor level: `iters` Adam steps on the one [E]
     appearance embedding of a test image, geometry and camera frozen.  -> (embedding [E] on the device, losses [iters], mses [iters] on the
     host).
@@ -1129,7 +1129,9 @@ def fit_appearance_embedding(rasterizer, means3D, opacities, scales, rotations, 
     `toned_colours(rows=...)`, `rasterizer(colors_precomp=...)` inside `colour_gradients_only(True)`, the loss ("dssim+l1":
     wg_fused_ssim.l1_ssim_loss with `lambda_dssim`; "mse"), `torch.optim.Adam(lr=lr)`.  `grad_scale` (the caller's scale_grads masks,
     multiplied together; broadcastable to the image) multiplies the image's cotangent and leaves its value unchanged.  The per-step losses
-    stay on the device; the host reads them once, at the end.  `campos` / `deg` default to the rasterizer's settings."""
+    stay on the device; the host reads them once, at the end.  `campos` / `deg` default to the rasterizer's settings.
+    `fixed_order=True`: the loop runs inside `colour_gradients_only("fixed_order")` -- the colour-only backward pass without float atomics.
+    Every other link of a step is reproducible already, so two calls then return the same embedding, losses and MSEs bit for bit."""
     from diff_gaussian_rasterization import colour_gradients_only
     from wg_fused_ssim import l1_ssim_loss
     if loss not in ("dssim+l1", "mse"):
@@ -1150,7 +1152,7 @@ def fit_appearance_embedding(rasterizer, means3D, opacities, scales, rotations, 
     optimizer = torch.optim.Adam([param], lr=lr)
     iters = int(iters)
     record = torch.zeros((2, max(iters, 1)), dtype=torch.float32, device=means3D.device)
-    with torch.enable_grad(), colour_gradients_only(True):
+    with torch.enable_grad(), colour_gradients_only("fixed_order" if fixed_order else True):
         for i in range(iters):
             optimizer.zero_grad()
             colours = toned_colours(features, gembedding, param, means3D, campos, weights, deg, rows=rows, pre_clamp_max=pre_clamp_max,

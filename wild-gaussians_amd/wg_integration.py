@@ -74,6 +74,8 @@ needs the few-line edits INTEGRATION.md lists.  What IS swapped, each with the r
                         `WildGaussians.optimize_embedding` (method.py:1755-1830: 128 render-and-backward steps per test image whose only
                         parameter is the appearance embedding, reached through `colors_precomp`) runs inside
                         `diff_gaussian_rasterization.colour_gradients_only(True)`: every backward pass is the colour-only one
+                        `embedding_optim="fixed_order"`: inside `colour_gradients_only("fixed_order")` instead -- no float atomics, so two fits of
+                        one checkpoint and image end at the same embedding, bit for bit (docs/OPTIONS.md)
                         Not with `edited_module` (ValueError): its render passes a second colour set or SH colours, which that pass refuses
   geometry_reuse        library option "geometry_reuse" = 1 (opt-in since round 4): the toned and depth calls of `_render_internal`
                         (method.py:1573-1631) ride on the raw call's projection and binning.  The caller's training loop qualifies
@@ -114,7 +116,7 @@ import torch
 
 def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True, densification_stats: bool = True, activations: bool = True,
                  eval_sh: bool = True, geometry_reuse: bool = True, edited_module=None, filter_3d: bool = False, densify: bool = False,
-                 embedding_optim: bool = False, uncertainty_loss: bool = False, uncertainty_backbone: bool = False,
+                 embedding_optim=False, uncertainty_loss: bool = False, uncertainty_backbone: bool = False,
                  uncertainty_feature_cache: bool = False, appearance_mlp: bool = False, uncertainty_metrics: bool = False):
     """-> a function that restores everything that was replaced.  `model`: an already constructed GaussianModel (e.g.
     `WildGaussians(...).model`) whose existing optimizer should be adopted too.
@@ -301,6 +303,9 @@ def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True
         swap(EM, "forward", embedding_forward)
 
     if embedding_optim:
+        if isinstance(embedding_optim, str) and embedding_optim != "fixed_order":
+            raise ValueError(f"embedding_optim is True, False or 'fixed_order', not {embedding_optim!r}")
+        colour_mode = "fixed_order" if isinstance(embedding_optim, str) else True
         if edited_module is not None:   # its _render_internal passes colors_precomp2= / shs= + sh_second=, which the colour-only pass refuses
             raise ValueError("embedding_optim cannot be combined with edited_module: the edited _render_internal makes calls the colour-only "
                              "backward pass refuses (a second colour set, SH colours with tones)")
@@ -309,7 +314,7 @@ def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True
 
         def optimize_embedding(self, *args, **kwargs):
             from diff_gaussian_rasterization import colour_gradients_only
-            with colour_gradients_only(True):
+            with colour_gradients_only(colour_mode):
                 return orig_optimize_embedding(self, *args, **kwargs)
         swap(WG, "optimize_embedding", optimize_embedding)
 
