@@ -656,6 +656,8 @@ struct FrameMode { const void* image; int exact; int row; const void* geom; size
 std::atomic<uint64_t> g_row_frames{0}, g_row_backwards{0};
 // ... forward calls whose render launch cleared the gradient record, backward calls that found it clean and cleared nothing
 std::atomic<uint64_t> g_clean_frames{0}, g_clean_backwards{0};
+// ... backward calls whose per-tile launch zeroed dL_dsh for a per-Gaussian kernel that stored the touched rows only (wg_common.h: WG_SH_GRAD_SKIP)
+std::atomic<uint64_t> g_sh_skip_backwards{0};
 std::mutex g_mode_mu;
 FrameMode g_modes[64];
 unsigned g_mode_head = 0;
@@ -1280,13 +1282,23 @@ static int backward_impl(const wg_backward_args& a) {
         hipError_t e = hipMemsetAsync(geom.grad_rec, 0, (size_t)P * (wg::GRAD_REC_FLOATS + (dual ? 1 : 0)) * sizeof(float), stream);
         if (e != hipSuccess) return hip_fail(e, "gradient record memset");
     }
+    // dL_dsh zeroed under the per-tile pass, only its touched rows stored by the per-Gaussian kernel (wg_common.h: WG_SH_GRAD_SKIP): both halves
+    // are decided here, in one call -- no state between calls, so a retained graph's second call and a captured one fill and store like any other.
+    // Plain SH colours of either backward mode; the toned kernels and the two-colour walk write every row as before, and so does a frame
+    // with nothing rendered (no per-tile launch to fill under).  Whether the caller WANTS dL_dsh this function cannot tell: with SH colours the
+    // pointer is required (above) and both bindings always pass a tensor, so a call whose shs do not require a gradient takes the path too --
+    // the same fill, fewer rows stored, a tensor nobody reads.
+    const bool sh_fill = WG_SH_GRAD_SKIP != 0 && R > 0 && shs != nullptr && dL_dsh != nullptr && tone == nullptr && tone2 == nullptr && !sh_second && !dual;
+    const bool nt_stream = opt.sh_stream == 1 || (opt.sh_stream < 0 && P <= opt.sh_stream_max_p);
+    if (sh_fill) g_sh_skip_backwards.fetch_add(1, std::memory_order_relaxed);
     if (R > 0) {
         // what the ordering launch clears on the side: the gradient records -- or, deterministic mode, the slots' flag bytes
         float* const clear_ptr = det ? reinterpret_cast<float*>(det_flags) : (clear_records ? geom.grad_rec : nullptr);
         const size_t clear_floats = det ? ((size_t)R + 3) / 4 : (size_t)P * (wg::GRAD_REC_FLOATS + (dual ? 1 : 0));
         WG_STAGE(WG_STAGE_TILE_RANGES, wg::launch_tile_order(img.tile_last, nullptr, img.order_bwd, gx * gy, clear_ptr, clear_floats, opt.backward_order_period, stream), "tile_order");
         WG_STAGE(WG_STAGE_RENDER_BACKWARD, wg::launch_render_backward(width, height, gx, gy, img, bin, geom, subpixel_offset, background, dL_dpix,
-                                            dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, record, opt.exact_compositing != 0, dual ? second->dL_dpix2 : nullptr, det_slots, det_flags, (size_t)R, P, stream),
+                                            dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, record, opt.exact_compositing != 0, dual ? second->dL_dpix2 : nullptr, det_slots, det_flags, (size_t)R, P, stream,
+                                            sh_fill ? dL_dsh : nullptr, sh_fill ? (size_t)P * (size_t)M * 3 : 0, WG_SH_GRAD_FILL_NT != 0 && nt_stream),
                  "render_backward");
     }
 
@@ -1309,7 +1321,8 @@ static int backward_impl(const wg_backward_args& a) {
     bp.kernel_size = kernel_size; bp.radii = radii;
     bp.dL_dcolor2 = dual ? second->dL_dcolor2 : nullptr;
     if (raw != nullptr) { bp.filter_3D = raw->filter_3D; bp.raw_opacities = raw->raw_opacities; }
-    bp.nt_stream = opt.sh_stream == 1 || (opt.sh_stream < 0 && P <= opt.sh_stream_max_p);
+    bp.nt_stream = nt_stream;
+    bp.dsh_zeroed = sh_fill;
     WG_STAGE(WG_STAGE_PREPROCESS_BACKWARD, wg::launch_preprocess_backward(bp, device_tone(tone, tone2, sh_second && dual), geom, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
                                             dL_dscale, dL_drot, record, stream),
              "preprocess_backward");
@@ -1619,6 +1632,8 @@ int wg_get_option(const char* name) {
     // ... forward calls whose render launch zeroed the gradient record / backward calls that found it clean and cleared nothing
     if (std::strcmp(name, "record_clean_frames") == 0) return (int)std::min<uint64_t>(g_clean_frames.load(std::memory_order_relaxed), 0x7fffffffu);
     if (std::strcmp(name, "record_clean_calls") == 0) return (int)std::min<uint64_t>(g_clean_backwards.load(std::memory_order_relaxed), 0x7fffffffu);
+    // ... backward calls whose per-tile launch zeroed dL_dsh and whose per-Gaussian kernel stored the touched rows only
+    if (std::strcmp(name, "sh_grad_skip_calls") == 0) return (int)std::min<uint64_t>(g_sh_skip_backwards.load(std::memory_order_relaxed), 0x7fffffffu);
     const OptionRow* r = find_option(name);
     return r ? r->get(options_snapshot()) : -1;
 }

@@ -9,7 +9,8 @@
 // M == 16 the wave instead moves its 64 Gaussians' 12 KiB block with 16-byte coalesced accesses and transposes
 // it through LDS (row pitch 52 floats = 13 float4: conflict-free ds_read/ds_write_b128 for every 16-lane group).
 // Every output except the four accumulation targets of the per-tile pass is fully written here (zeros for culled
-// Gaussians), so the caller does not have to clear them.
+// Gaussians), so the caller does not have to clear them.  One exception (BwdParams::dsh_zeroed, wg_common.h: WG_SH_GRAD_SKIP): the per-tile
+// pass that ran before has zeroed dL_dsh on the side, and only the rows with a non-zero dL_dRGB -- a third of them at the headline frame -- are stored.
 //
 // The formulas are the reference's hand-derived ones, including its quirks:
 //  - dL_dopacity arrives w.r.t. the mip-filtered opacity and leaves multiplied by coef (or zeroed when the
@@ -367,6 +368,10 @@ __global__ void __launch_bounds__(64) preprocess_backward_kernel(
 #pragma unroll
         for (int k = 0; k < 48; k++) dsh[k] = 0.f;
     }
+    // BwdParams::dsh_zeroed: dL_dsh[k][ch] = B[k] * dL_dRGB[ch] arrives zeroed, so only a row with a non-zero dL_dRGB (after the clamp flags; a
+    // NaN compares unequal and is stored) carries anything.  Stores alone are left out: loads, arithmetic and every other output are as ever.
+    const bool skip = !TONE && p.dsh_zeroed;   // wave-uniform (the toned kernels write every row: api.hip does not set the flag for them)
+    bool sh_row = false;
     if (vis && p.shs != nullptr) {
         float ox = mx - camx, oy = my - camy, oz = mz - camz;
         float sum2 = ox * ox + oy * oy + oz * oz;
@@ -380,6 +385,8 @@ __global__ void __launch_bounds__(64) preprocess_backward_kernel(
         if constexpr (ROW) sh_basis_exact(p.D, ox * ilen, oy * ilen, oz * ilen, B, Dx, Dy, Dz);
         else sh_basis(p.D, ox * ilen, oy * ilen, oz * ilen, B, Dx, Dy, Dz);
         const float dRGB[3] = {(cl & 1) ? 0.f : dcol0, (cl & 2) ? 0.f : dcol1, (cl & 4) ? 0.f : dcol2};
+        sh_row = dRGB[0] != 0.f || dRGB[1] != 0.f || dRGB[2] != 0.f;
+        const bool store_row = !skip || sh_row;   // the generic layout's per-row stores (the coalesced layouts decide by ballot, at the write-out)
         float ddx = 0.f, ddy = 0.f, ddz = 0.f;  // dL_ddir
         // TONE with a second set (ShTone::second): the same coefficients fed a second colour through tone 2; its dL/dRGB are the record's
         // floats 10, 11 and grad_aux (render_bwd.hip: DUAL), its clamp flags bits 3-5.  Both chains add into dL_dsh and dL_ddir.
@@ -417,7 +424,7 @@ __global__ void __launch_bounds__(64) preprocess_backward_kernel(
                 for (int k = 0; k < 16; k++)
 #pragma unroll
                     for (int ch = 0; ch < 3; ch++) dsh[3 * k + ch] = B[k] * dRGB[ch];
-            } else {
+            } else if (store_row) {
                 float* d = dL_dsh + (size_t)idx * p.M * 3;
                 const int ncoef = (p.D + 1) * (p.D + 1);
                 for (int k = 0; k < p.M; k++) {
@@ -508,7 +515,7 @@ __global__ void __launch_bounds__(64) preprocess_backward_kernel(
                             w += val2 * dRGB2[ch];
                         }
                     }
-                    d[3 * k + ch] = g;
+                    if (store_row) d[3 * k + ch] = g;
                     ddx += dxk * w;
                     ddy += dyk * w;
                     ddz += dzk * w;
@@ -528,7 +535,7 @@ __global__ void __launch_bounds__(64) preprocess_backward_kernel(
         dL_dmean3D[3 * idx] = gmx;
         dL_dmean3D[3 * idx + 1] = gmy;
         dL_dmean3D[3 * idx + 2] = gmz;
-        if (!FAST_SH && p.shs != nullptr && !vis) {
+        if (!FAST_SH && p.shs != nullptr && !vis && !skip) {
             float* d = dL_dsh + (size_t)idx * p.M * 3;
             for (int k = 0; k < p.M * 3; k++) d[k] = 0.f;
         }
@@ -543,6 +550,8 @@ __global__ void __launch_bounds__(64) preprocess_backward_kernel(
         }
     }
     if (FAST_SH) {
+        // dsh_zeroed: one bit per Gaussian of the wave (every lane is here: the ballot is wave-wide); float4 f of the block belongs to row f / 12
+        const uint64_t rows = skip ? __ballot(sh_row) : ~0ull;
         __syncthreads();  // every lane has consumed its SH inputs
 #pragma unroll
         for (int qd = 0; qd < 12; qd++)
@@ -553,7 +562,7 @@ __global__ void __launch_bounds__(64) preprocess_backward_kernel(
 #pragma unroll
         for (int i = 0; i < 12; i++) {
             const int f = i * 64 + lane;
-            if (f < nvalid) stream_store4<NT>(&dst[f], stage[(f / 12) * SH_PITCH4 + (f % 12)]);
+            if (f < nvalid && ((rows >> (f / 12)) & 1ull)) stream_store4<NT>(&dst[f], stage[(f / 12) * SH_PITCH4 + (f % 12)]);
         }
     }
 }

@@ -178,6 +178,30 @@ __device__ unsigned long long g_bwd_probe[4 * 65536];
 #ifndef WG_BWD_LDS_REDUCE
 #define WG_BWD_LDS_REDUCE 1
 #endif
+// The launch zeroes fill[0 .. n) on the side (dL_dsh for the per-Gaussian kernel, wg_common.h: WG_SH_GRAD_SKIP): the kernel is bound by vector
+// issue and leaves the memory system nearly idle, the per-Gaussian kernel that would otherwise write these zeros is bound by its bytes.  Every
+// wave zeroes one contiguous share of the 16-byte-aligned body, per_wave float4 from float4 blockIdx.x * per_wave on, as its LAST act -- the
+// way render_fwd.hip's fwd_clear_record deals the gradient record (as a wave's first act, or as a burst from extra workgroups, the same
+// stores were measured to cost the walk several us: EXPERIMENTS.md R9.1) -- when no register of the walk is live.  What is not a whole
+// aligned float4 -- up to three floats in front of the body when the pointer is not 16-byte aligned, up to three behind it (the generic
+// layout's 3 M P floats) -- is stored float by float by wave 0.  Bounds: body float4 i covers floats head + 4 i .. head + 4 i + 3 with
+// i < nvec = (n - head) / 4, the tail floats head + 4 nvec + lane < n.
+__device__ __forceinline__ void bwd_fill_zero(float* __restrict__ fill, size_t n, uint32_t per_wave, int nt) {
+    if (!fill) return;
+    const size_t head = min((size_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(fill) & 15u)) & 15u) / 4, n);   // (a float pointer: 4-byte aligned)
+    const size_t nvec = (n - head) / 4;
+    float4* const body = reinterpret_cast<float4*>(fill + head);
+    const size_t begin = (size_t)blockIdx.x * per_wave;
+    const size_t stop = begin + per_wave < nvec ? begin + per_wave : nvec;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (nt) { for (size_t i = begin + threadIdx.x; i < stop; i += 64) stream_store4<true>(&body[i], z); }
+    else { for (size_t i = begin + threadIdx.x; i < stop; i += 64) body[i] = z; }
+    if (blockIdx.x == 0) {
+        const size_t tail = head + 4 * nvec;
+        if (threadIdx.x < head) fill[threadIdx.x] = 0.f;
+        if (tail + threadIdx.x < n) fill[tail + threadIdx.x] = 0.f;
+    }
+}
 template <bool RECORD, bool DET = false, bool EXACT = false, bool DUAL = false>
 __global__ void __launch_bounds__(64) WG_BWD_OCC
 #if WG_BWD_DUAL_WAVES
@@ -190,7 +214,8 @@ render_backward_kernel(
     const float* __restrict__ dL_dpix, float* __restrict__ dL_dmean2D, float* __restrict__ dL_dconic,
     float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolor, float* __restrict__ grad_rec,
     const ushort4* __restrict__ rects, const uint32_t* __restrict__ offsets_incl, const uint32_t* __restrict__ tiles_touched,
-    float* __restrict__ det_slots, unsigned char* __restrict__ det_flags, const float* __restrict__ dL_dpix2, float* __restrict__ grad_aux) {
+    float* __restrict__ det_slots, unsigned char* __restrict__ det_flags, const float* __restrict__ dL_dpix2, float* __restrict__ grad_aux,
+    float* __restrict__ fill, size_t fill_floats, uint32_t fill_per_wave, int fill_nt) {
     static_assert(!DUAL || RECORD, "the two-colour walk accumulates into the gradient record (or, DET, into fourteen-float slots)");
     constexpr int SLOT_FLOATS = DUAL ? 14 : 10;   // deterministic mode: floats per (tile, Gaussian) slot (thirteen sums, padded to 8-byte multiples)
     constexpr int RS = DUAL ? 4 : 3;   // float4 per parked record
@@ -213,7 +238,10 @@ render_backward_kernel(
         g_bwd_probe[4 * blockIdx.x + 2] = ((unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32) | (unsigned)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
     }
 #endif
-    if (hi0 == 0) return;
+    if (hi0 == 0) {   // nothing to walk: the wave's share of the fill is all it does
+        bwd_fill_zero(fill, fill_floats, fill_per_wave, fill_nt);
+        return;
+    }
     const int lane = threadIdx.x;
     const int tx = tile % gx, ty = tile / gx;
     const size_t plane = (size_t)W * H;
@@ -497,6 +525,7 @@ render_backward_kernel(
             if (DUAL) ac2r = ac2g = ac2b = 0.f;
         }
     }
+    bwd_fill_zero(fill, fill_floats, fill_per_wave, fill_nt);
 #if WG_COUNT_PAIRS
     if (lane == 0)
         for (int i = 0; i < 14; i++) atomicAdd(&g_bwd_counters[i], wgc[i]);
@@ -654,14 +683,17 @@ hipError_t launch_render_backward(int W, int H, int gx, int gy, const ImageState
                                   const GeometryState& g, const float* subpixel_offset, const float* background,
                                   const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
                                   float* dL_dcolor, bool record, bool exact, const float* dL_dpix2, float* det_slots, unsigned char* det_flags, size_t slot_capacity, int P,
-                                  hipStream_t stream) {
+                                  hipStream_t stream, float* fill, size_t fill_floats, bool fill_nt) {
     const int tiles = gx * gy;
     if (tiles <= 0) return hipSuccess;
+    // the fill's share of a wave, in float4 (bwd_fill_zero): the aligned body has at most fill_floats / 4 of them
+    const uint32_t fill_per_wave = fill ? (uint32_t)((fill_floats / 4 + (size_t)tiles - 1) / (size_t)tiles) : 0u;
 #define WG_LAUNCH3(REC, DET, EX, DU)                                                                                                            \
     hipLaunchKernelGGL((render_backward_kernel<REC, DET, EX, DU>), dim3(tiles), dim3(64), 0, stream, W, H, gx, tiles, img.order_bwd, img.ranges,     \
                        b.point_list, g.splats, reinterpret_cast<const float2*>(subpixel_offset), background, img.final_T, img.n_contrib,    \
                        img.tile_last, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, g.grad_rec, g.rects, g.point_offsets,         \
-                       g.tiles_touched, det_slots, det_flags, dL_dpix2, g.grad_rec + (size_t)P * GRAD_REC_FLOATS)
+                       g.tiles_touched, det_slots, det_flags, dL_dpix2, g.grad_rec + (size_t)P * GRAD_REC_FLOATS, fill, fill_floats, fill_per_wave,    \
+                       fill_nt ? 1 : 0)
 #define WG_LAUNCH2(REC, DET, EX) WG_LAUNCH3(REC, DET, EX, false)
 #define WG_LAUNCH(REC, DET) do { if (exact) WG_LAUNCH2(REC, DET, true); else WG_LAUNCH2(REC, DET, false); } while (0)
     if (dL_dpix2 && det_slots) {   // two colour sets, deterministic: fourteen-float slots

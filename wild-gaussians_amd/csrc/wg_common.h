@@ -460,7 +460,20 @@ hipError_t launch_render_backward(int W, int H, int gx, int gy, const ImageState
                                   const GeometryState& g, const float* subpixel_offset, const float* background,
                                   const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
                                   float* dL_dcolor, bool record, bool exact, const float* dL_dpix2, float* det_slots, unsigned char* det_flags, size_t slot_capacity, int P,
-                                  hipStream_t stream);  // det_slots != nullptr: deterministic mode (det_flags: one byte per slot, cleared)
+                                  hipStream_t stream, float* fill = nullptr, size_t fill_floats = 0, bool fill_nt = false);
+// det_slots != nullptr: deterministic mode (det_flags: one byte per slot, cleared)
+// fill != nullptr: the launch also zeroes fill[0 .. fill_floats), every wave one contiguous share as its last act (render_bwd.hip: bwd_fill_zero;
+// fill_nt: with non-temporal stores) -- dL_dsh for the per-Gaussian kernel that follows (BwdParams::dsh_zeroed)
+// WG_SH_GRAD_SKIP (api.hip: backward_impl decides both halves in one call): 1 = dL_dsh is zeroed under the per-tile pass, whose memory system is
+// nearly idle, and the per-Gaussian kernel -- bound by the bytes it moves -- stores only the rows something was added to; 0 = the per-Gaussian
+// kernel writes every row (A/B: a variant build with -DWG_SH_GRAD_SKIP=0).  WG_SH_GRAD_FILL_NT: the fill's stores are non-temporal whenever
+// the per-Gaussian streams are (option "sh_stream"); 0 = always plain.
+#ifndef WG_SH_GRAD_SKIP
+#define WG_SH_GRAD_SKIP 1
+#endif
+#ifndef WG_SH_GRAD_FILL_NT
+#define WG_SH_GRAD_FILL_NT 1
+#endif
 // the colour-only backward pass (render_bwd.hip: render_backward_colour_kernel): dL_dcolor[3 P] += the forward pass's blend weights times dL_dpix, over each tile's
 // first tile_last entries in img.order_bwd's order; dL_dcolor must arrive cleared
 hipError_t launch_render_backward_colour(int W, int H, int gx, int gy, const ImageState& img, const BinningState& b, const GeometryState& g,
@@ -495,6 +508,7 @@ struct BwdParams {
     const float* filter_3D = nullptr;      // raw-parameter mode: scales / rotations above are RAW, raw_opacities the raw opacities; dL_dscale /
     const float* raw_opacities = nullptr;  // dL_drot / dL_dopacity come out as the gradients of the RAW parameters
     bool nt_stream = false;                // the SH block in and dL_dsh out as non-temporal accesses (stream_load4 / stream_store4)
+    bool dsh_zeroed = false;               // dL_dsh arrives zeroed (launch_render_backward's fill): only rows with a non-zero dL_dRGB are stored (untoned kernels)
 };
 // record: the four arrays are OUTPUTS computed from g.grad_rec (see GRAD_REC_*); otherwise inputs accumulated by the per-tile pass
 hipError_t launch_preprocess_backward(const BwdParams& p, const ShTone& tone, const GeometryState& g, float* dL_dmean2D,
