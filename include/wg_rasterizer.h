@@ -187,6 +187,25 @@ typedef struct wg_forward_args {
     const wg_call_options* options;
 } wg_forward_args;
 
+/* The gradient of the depth pass (wg_render_depth) inside the frame's backward call: one more per-tile walk that adds into the gradient record
+ * before the per-Gaussian kernel runs, so that dL_dmean2D / dL_dopacity / dL_dmean3D / dL_dcov3D / dL_dscale / dL_drot come out as the gradients of
+ * the image loss PLUS the depth loss (what autograd adds over the image call and a second three-channel call with the scalars as colours).
+ *   depth = sum_i v_i alpha_i T_i over the pairs the forward call blended:  dL/dv_g = sum over g's pairs of alpha T dL_ddepth[pixel];
+ *   dL/dalpha_i = dL_ddepth[pixel] T_i (v_i - R_i), R_i the reference's accum_rec recursion for one channel (backward.cu:555-561); no background
+ *   term; from dL/dalpha on the reference's chain (backward.cu:568-603).  The abs-gradient (dL_dmean2D.z) receives |q_depth| beside |q_image|.
+ *   values: float[P], the scalars of the forward depth pass; or NULL = the distance to the camera (reads the call's means3D and campos): dL_dmean3D
+ *     then also receives dL_dvalues[g] * (x_g - campos) / v_g (0 where v_g == 0).  campos takes no gradient.
+ *   dL_dvalues: float[P], required in both modes, overwritten in full, zero for Gaussians without instances.
+ * Needs the atomic gradient record: WG_ERR_INVALID_ARGUMENT, before any launch, with colour_gradients_only != 0, deterministic_backward = 1,
+ * grad_record = 0, a struct_size smaller than the struct, a NULL dL_ddepth or (P > 0) dL_dvalues, distance mode without means3D / campos.  R = 0 or
+ * P = 0 zero-fill dL_dvalues and launch no walk.  No scratch, no host wait: the call captures like the one without the block. */
+typedef struct wg_depth_grad {
+    size_t struct_size;       /* the CALLER's sizeof(wg_depth_grad): fields are only ever appended */
+    const float* dL_ddepth;   /* [H*W] */
+    const float* values;      /* [P] or NULL (distance) */
+    float* dL_dvalues;        /* [P], fully overwritten */
+} wg_depth_grad;
+
 typedef struct wg_backward_args {
     size_t struct_size;
     int P, D, M, R, width, height, debug;
@@ -217,6 +236,8 @@ typedef struct wg_backward_args {
                                           bits.  Same needs and refusals as 1 (deterministic_backward = 1 included: that option belongs to the
                                           full pass); additionally refused inside a stream capture, like the full pass's deterministic mode.
                                           Any other non-zero value behaves as 1. */
+    const wg_depth_grad* depth;        /* the depth pass's gradient in the same call (wg_depth_grad above), or NULL.  Absent (a struct of 320 bytes or
+                                          less) = NULL: the call runs no new code and its gradients have the bits they had. */
 } wg_backward_args;
 #define WG_COLOUR_GRADIENTS_ATOMIC 1
 #define WG_COLOUR_GRADIENTS_FIXED_ORDER 2
@@ -262,7 +283,8 @@ int wg_view_image(char* image_buffer, int width, int height, wg_image_view* out)
 
 /* ---- per-stage timing with HIP events on the caller's stream (bench.py's roofline): enable, run, read (synchronises) ---- */
 enum { WG_STAGE_PREPROCESS = 0, WG_STAGE_SCAN, WG_STAGE_DUPLICATE_KEYS, WG_STAGE_SORT, WG_STAGE_TILE_RANGES,
-       WG_STAGE_RENDER_FORWARD, WG_STAGE_RENDER_BACKWARD, WG_STAGE_PREPROCESS_BACKWARD, WG_STAGE_RENDER_FIXUP, WG_STAGE_RENDER_DEPTH, WG_STAGE_COUNT };
+       WG_STAGE_RENDER_FORWARD, WG_STAGE_RENDER_BACKWARD, WG_STAGE_PREPROCESS_BACKWARD, WG_STAGE_RENDER_FIXUP, WG_STAGE_RENDER_DEPTH, WG_STAGE_RENDER_DEPTH_BACKWARD,
+       WG_STAGE_COUNT };
 typedef struct wg_stage_times {
     double total_ms[WG_STAGE_COUNT];
     long long launches[WG_STAGE_COUNT];

@@ -37,6 +37,8 @@ SOURCES = {
                                                                            # the forward call's bits; in a subdirectory like the other opt-ins
     "depth/depth.hip": ["-fno-slp-vectorize"],   # the depth pass (wg_render_depth): the forward walk over a finished frame with one per-pixel sum;
                                                  # render_fwd.hip's flags, so that the sum has the forward kernel's instruction and its bits
+    "depth/depth_bwd.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],   # the depth pass's gradient (wg_depth_grad): render_bwd.hip's walk with one
+                                                                            # channel, adding into the same gradient record; render_bwd.hip's flags
     "binning.hip": ["-fno-slp-vectorize"],
     "render_fwd.hip": ["-fno-slp-vectorize"],
     "render_bwd.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],

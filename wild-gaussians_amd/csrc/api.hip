@@ -314,7 +314,7 @@ struct StageScope {
 const char* stage_label(int stage) {
     static const char* names[WG_STAGE_COUNT] = {"wg:K1 preprocess", "wg:K2-K3 scan", "wg:K4 duplicate_keys", "wg:K5 sort", "wg:K6-K7 tile_ranges",
                                                 "wg:K8 render_forward", "wg:K9 render_backward", "wg:K10-K11 preprocess_backward",
-                                                "wg:K8 render_fixup", "wg:K8d render_depth"};
+                                                "wg:K8 render_fixup", "wg:K8d render_depth", "wg:K9d render_depth_backward"};
     return (stage >= 0 && stage < WG_STAGE_COUNT) ? names[stage] : "wg:?";
 }
 
@@ -658,6 +658,7 @@ std::atomic<uint64_t> g_row_frames{0}, g_row_backwards{0};
 std::atomic<uint64_t> g_clean_frames{0}, g_clean_backwards{0};
 // ... backward calls whose per-tile launch zeroed dL_dsh for a per-Gaussian kernel that stored the touched rows only (wg_common.h: WG_SH_GRAD_SKIP)
 std::atomic<uint64_t> g_sh_skip_backwards{0};
+std::atomic<uint64_t> g_depth_grad_backwards{0};   // backward calls that ran the depth cotangent's walk (wg_depth_grad); read-only option "depth_grad_calls"
 std::mutex g_mode_mu;
 FrameMode g_modes[64];
 unsigned g_mode_head = 0;
@@ -1181,6 +1182,15 @@ static int backward_impl(const wg_backward_args& a) {
         const int fwd_mode = remembered_mode(image_buffer);
         if (fwd_mode >= 0 && fwd_mode != (opt.exact_compositing ? 1 : 0)) return WG_ERR_INVALID_ARGUMENT;
     }
+    // the depth pass's gradient (wg_depth_grad): one more walk that adds into the ATOMIC gradient record -- refused, before anything is launched,
+    // wherever there is no such record to add into
+    const wg_depth_grad* const dgrad = a.depth;
+    if (dgrad != nullptr) {
+        if (dgrad->struct_size < sizeof(wg_depth_grad)) return WG_ERR_INVALID_ARGUMENT;
+        if (a.colour_gradients_only != 0 || opt.deterministic_backward != 0 || opt.grad_record == 0) return WG_ERR_INVALID_ARGUMENT;
+        if (dgrad->dL_ddepth == nullptr || (P > 0 && dgrad->dL_dvalues == nullptr)) return WG_ERR_INVALID_ARGUMENT;
+        if (P > 0 && dgrad->values == nullptr && (means3D == nullptr || campos == nullptr)) return WG_ERR_INVALID_ARGUMENT;   // distance mode's inputs
+    }
     if (a.colour_gradients_only != 0) return backward_colour_impl(a, opt);
     // two colour sets over one walk: the thirteen sums go to the gradient record (or, deterministic mode, to fourteen-float slots)
     const bool dual = second != nullptr && P > 0;
@@ -1301,6 +1311,22 @@ static int backward_impl(const wg_backward_args& a) {
                                             sh_fill ? dL_dsh : nullptr, sh_fill ? (size_t)P * (size_t)M * 3 : 0, WG_SH_GRAD_FILL_NT != 0 && nt_stream),
                  "render_backward");
     }
+    // The depth cotangent's walk: the record is clear or holds this frame's image sums by now -- cleared by the forward launch (record_clean) or by
+    // the ordering launch above, both in front of it on the stream -- and the per-Gaussian kernel below has not read it yet.  dL_dvalues is an
+    // output: zeroed here, the walk adds into it.  Without instances (R == 0) the zeros are the result and no walk is launched.
+    if (dgrad != nullptr) {
+        {
+            StageScope scope_(WG_STAGE_RENDER_DEPTH_BACKWARD, stream);
+            hipError_t e = hipMemsetAsync(dgrad->dL_dvalues, 0, (size_t)P * sizeof(float), stream);
+            if (e != hipSuccess) return hip_fail(e, "dL_dvalues memset");
+        }
+        if (R > 0) {
+            g_depth_grad_backwards.fetch_add(1, std::memory_order_relaxed);
+            WG_STAGE(WG_STAGE_RENDER_DEPTH_BACKWARD, wg::launch_render_depth_backward(width, height, gx, gy, img, bin, geom, subpixel_offset, dgrad->dL_ddepth,
+                                                                                    dgrad->values, means3D, campos, dgrad->dL_dvalues,
+                                                                                    opt.exact_compositing != 0, stream), "render_depth_backward");
+        }
+    }
 
     wg::BwdParams bp;
     bp.P = P; bp.D = D; bp.M = M; bp.W = width; bp.H = height;
@@ -1326,6 +1352,9 @@ static int backward_impl(const wg_backward_args& a) {
     WG_STAGE(WG_STAGE_PREPROCESS_BACKWARD, wg::launch_preprocess_backward(bp, device_tone(tone, tone2, sh_second && dual), geom, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
                                             dL_dscale, dL_drot, record, stream),
              "preprocess_backward");
+    // distance mode: v = |x - campos| depends on the mean itself -- its direct term goes on top of what the per-Gaussian kernel wrote
+    if (dgrad != nullptr && dgrad->values == nullptr && R > 0)
+        WG_STAGE(WG_STAGE_RENDER_DEPTH_BACKWARD, wg::launch_depth_distance_fold(P, means3D, campos, dgrad->dL_dvalues, dL_dmean3D, stream), "depth_distance_fold");
     {
         hipError_t e = det_guard.release();
         if (e != hipSuccess) return hip_fail(e, "deterministic backward scratch release");
@@ -1634,6 +1663,7 @@ int wg_get_option(const char* name) {
     if (std::strcmp(name, "record_clean_calls") == 0) return (int)std::min<uint64_t>(g_clean_backwards.load(std::memory_order_relaxed), 0x7fffffffu);
     // ... backward calls whose per-tile launch zeroed dL_dsh and whose per-Gaussian kernel stored the touched rows only
     if (std::strcmp(name, "sh_grad_skip_calls") == 0) return (int)std::min<uint64_t>(g_sh_skip_backwards.load(std::memory_order_relaxed), 0x7fffffffu);
+    if (std::strcmp(name, "depth_grad_calls") == 0) return (int)std::min<uint64_t>(g_depth_grad_backwards.load(std::memory_order_relaxed), 0x7fffffffu);
     const OptionRow* r = find_option(name);
     return r ? r->get(options_snapshot()) : -1;
 }
@@ -1672,7 +1702,8 @@ int wg_profile_read(wg_stage_times* out) {
 
 const char* wg_stage_name(int stage) {
     static const char* names[WG_STAGE_COUNT] = {"preprocess", "scan", "duplicate_keys", "sort", "tile_ranges",
-                                                "render_forward", "render_backward", "preprocess_backward", "render_fixup", "render_depth"};
+                                                "render_forward", "render_backward", "preprocess_backward", "render_fixup", "render_depth",
+                                                "render_depth_backward"};
     return (stage >= 0 && stage < WG_STAGE_COUNT) ? names[stage] : "?";
 }
 

@@ -202,14 +202,14 @@ ForwardResult forward(const Scene& s, const torch::Tensor& opacity, const int H,
 
 // The reference's eight (rasterize_points.cu:201) and what the optional blocks add (undefined = not asked for).
 struct Gradients {
-    torch::Tensor means2D, colors, opacity, means3D, cov3D, sh, scales, rotations, colors2, mul, offset, mul2, offset2;
+    torch::Tensor means2D, colors, opacity, means3D, cov3D, sh, scales, rotations, colors2, mul, offset, mul2, offset2, values;   // values: with `depth` only
     std::vector<torch::Tensor> eight() const { return {means2D, colors, opacity, means3D, cov3D, sh, scales, rotations}; }
 };
 
 Gradients backward(const Scene& s, const torch::Tensor& radii, const torch::Tensor& dL_dout_color, const torch::Tensor& geomBuffer, const int R,
                    const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const py::object& sh_tone, const OptTensor& dL_dout_color2,
                    const py::object& raw_in, const py::object& sh_second, const wg_call_options& co, const int colour_only = 0,   // (wg_backward_args::colour_gradients_only)
-                   const bool want_colors = true, const bool want_cov3D = true) {
+                   const bool want_colors = true, const bool want_cov3D = true, const py::object& depth = py::none()) {   // depth: wg_depth_grad
     const auto dev = s.means3D.device();
     const c10::DeviceGuard guard(dev);
     const int P = static_cast<int>(s.means3D.size(0));
@@ -233,6 +233,32 @@ Gradients backward(const Scene& s, const torch::Tensor& radii, const torch::Tens
         rop = f32(tu[1].cast<torch::Tensor>(), dev);
         if (f3d.numel() != P64 || rop.numel() != P64) throw std::runtime_error("raw = (filter_3D, raw_opacities) must have P elements each");
         raw.filter_3D = ptr(f3d); raw.raw_opacities = ptr(rop);
+    }
+    // depth = None | (dL_ddepth [H, W], source): the checks of _C.py's _check_depth_grad_arguments, in its order, with its messages
+    torch::Tensor dLd, dvalues;
+    bool depth_distance = false;
+    if (!depth.is_none()) {
+        const char* source_msg = "return_depth must be \"distance\" or a float32 [P] tensor of per-Gaussian scalars on the frame's HIP device";
+        const char* block_msg = "depth is (dL_ddepth, source): the depth cotangent [H, W] and the frame's return_depth source";
+        const char* cot_msg = "dL_ddepth must be a float32 tensor of H * W elements on the frame's HIP device";
+        if (!(py::isinstance<py::tuple>(depth) || py::isinstance<py::list>(depth)) || py::len(depth) != 2) throw std::runtime_error(block_msg);
+        const py::sequence sq = depth.cast<py::sequence>();
+        const py::object cot = sq[0], source = sq[1];
+        if (!THPVariable_Check(cot.ptr())) throw std::runtime_error(cot_msg);
+        dLd = cot.cast<torch::Tensor>();
+        if (dLd.scalar_type() != torch::kFloat32 || dLd.numel() * 3 != dL_dout_color.numel() || dLd.device() != dL_dout_color.device()) throw std::runtime_error(cot_msg);
+        depth_distance = py::isinstance<py::str>(source);
+        if (depth_distance) {
+            if (source.cast<std::string>() != "distance") throw std::runtime_error(source_msg);
+        } else {
+            if (!THPVariable_Check(source.ptr())) throw std::runtime_error(source_msg);
+            dvalues = source.cast<torch::Tensor>();
+            if (dvalues.scalar_type() != torch::kFloat32) throw std::runtime_error(source_msg);
+            if (dvalues.numel() != P64) throw std::runtime_error("depth values must have P elements");
+            if (!dvalues.is_cuda() || dvalues.device() != dL_dout_color.device()) throw std::runtime_error(source_msg);
+            dvalues = dvalues.contiguous();
+        }
+        dLd = dLd.contiguous();
     }
 
     const int H = static_cast<int>(dL_dout_color.size(1)), W = static_cast<int>(dL_dout_color.size(2));
@@ -280,6 +306,7 @@ Gradients backward(const Scene& s, const torch::Tensor& radii, const torch::Tens
     if (tone.t.offset) g.offset = alloc({P, 3}, true);
     if (tone2.t.mul) g.mul2 = alloc({P, 3}, true);
     if (tone2.t.offset) g.offset2 = alloc({P, 3}, true);
+    if (!depth.is_none()) g.values = alloc({P}, true);   // (the library fills it)
     if (P == 0) return g;
 
     tone.t.dL_dmul = const_cast<float*>(ptr(g.mul)); tone.t.dL_doffset = const_cast<float*>(ptr(g.offset));
@@ -306,6 +333,12 @@ Gradients backward(const Scene& s, const torch::Tensor& radii, const torch::Tens
         a.second = &second;
     }
     if (!raw_in.is_none()) a.raw = &raw;
+    wg_depth_grad dgrad{};
+    if (!depth.is_none()) {   // the cotangent, the scalars (NULL = distance: the call's means3D and campos) and their gradient
+        dgrad.struct_size = sizeof(dgrad);
+        dgrad.dL_ddepth = dLd.data_ptr<float>(); dgrad.values = depth_distance ? nullptr : dvalues.data_ptr<float>(); dgrad.dL_dvalues = g.values.data_ptr<float>();
+        a.depth = &dgrad;
+    }
     int status;
     {
         py::gil_scoped_release nogil;   // (as the forward call: a deferred frame's verdict may be waited for here)
@@ -504,8 +537,9 @@ py::tuple RasterizeGaussiansExNoHint(const torch::Tensor& background, const torc
                                 colors2, filter_3D, sh_second, options, false);
 }
 
-// -> the reference's eight, + (mul, offset, mul2, offset2) with sh_second, + dL_dcolors2 with a second colour set, + (mul, offset) with sh_tone
-py::tuple RasterizeGaussiansBackwardEx(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& colors,
+// -> the reference's eight, + (mul, offset, mul2, offset2) with sh_second, + dL_dcolors2 with a second colour set, + (mul, offset) with sh_tone,
+//    + dL_dvalues [P] last with the depth block (depth = None: absent)
+py::tuple RasterizeGaussiansBackwardDepth(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& colors,
                                        const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier,
                                        const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix,
                                        const float tan_fovx, const float tan_fovy, const float kernel_size, const OptTensor& subpixel_offset,
@@ -513,11 +547,11 @@ py::tuple RasterizeGaussiansBackwardEx(const torch::Tensor& background, const to
                                        const torch::Tensor& geomBuffer, const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
                                        const bool debug, const py::object& sh_tone, const OptTensor& dL_dout_color2, const py::object& raw_in,
                                        const py::object& sh_second, const std::tuple<int, int, int>& options, const bool want_colors,
-                                       const bool want_cov3D) {
+                                       const bool want_cov3D, const py::object& depth) {
     const Scene s{background, means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, kernel_size,
                   opt(subpixel_offset), sh, degree, campos, debug};
     const Gradients g = backward(s, radii, dL_dout_color, geomBuffer, R, binningBuffer, imageBuffer, sh_tone, dL_dout_color2, raw_in, sh_second,
-                                 call_options(options), 0, want_colors, want_cov3D);
+                                 call_options(options), 0, want_colors, want_cov3D, depth);
     py::list out;
     for (const auto& t : g.eight()) out.append(or_none(t));   // (None: dL_dcolors / dL_dcov3D that the caller did not want)
     if (!sh_second.is_none()) {
@@ -527,7 +561,23 @@ py::tuple RasterizeGaussiansBackwardEx(const torch::Tensor& background, const to
     } else if (!sh_tone.is_none()) {
         out.append(or_none(g.mul)); out.append(or_none(g.offset));
     }
+    if (!depth.is_none()) out.append(g.values);   // + dL_dvalues [P], last
     return py::tuple(out);
+}
+
+// (without the depth block: today's call)
+py::tuple RasterizeGaussiansBackwardEx(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& colors,
+                                       const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier,
+                                       const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix,
+                                       const float tan_fovx, const float tan_fovy, const float kernel_size, const OptTensor& subpixel_offset,
+                                       const torch::Tensor& dL_dout_color, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
+                                       const torch::Tensor& geomBuffer, const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
+                                       const bool debug, const py::object& sh_tone, const OptTensor& dL_dout_color2, const py::object& raw_in,
+                                       const py::object& sh_second, const std::tuple<int, int, int>& options, const bool want_colors,
+                                       const bool want_cov3D) {
+    return RasterizeGaussiansBackwardDepth(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
+                                           tan_fovy, kernel_size, subpixel_offset, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
+                                           debug, sh_tone, dL_dout_color2, raw_in, sh_second, options, want_colors, want_cov3D, py::none());
 }
 
 // (callers from before the two "wanted" flags: all eight)
@@ -572,4 +622,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {   // ext.cpp:15-19
     m.def("rasterize_gaussians_backward_ex", &RasterizeGaussiansBackwardEx);   // + the blocks of wg_backward_args, + which of dL_dcolors / dL_dcov3D the caller wants
     m.def("rasterize_gaussians_backward_ex", &RasterizeGaussiansBackwardExAll);   //   (overload without the two flags: all eight)
     m.def("rasterize_gaussians_backward_colour", &RasterizeGaussiansBackwardColour);   // wg_backward_args::colour_gradients_only
+    m.def("rasterize_gaussians_backward_depth", &RasterizeGaussiansBackwardDepth);     // + wg_backward_args::depth: (dL_ddepth, source) -> ..., dL_dvalues
 }

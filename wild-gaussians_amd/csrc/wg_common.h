@@ -489,6 +489,15 @@ hipError_t launch_render_backward_colour_fixed(int W, int H, int gx, int gy, con
 hipError_t launch_render_depth(int W, int H, int gx, int gy, const ImageState& img, const BinningState& b, const GeometryState& g,
                                const float* subpixel_offset, const float* values, const float* means3D, const float* campos, float* depth,
                                bool exact, hipStream_t stream);
+// the depth pass's gradient (depth/depth_bwd.hip: render_depth_backward_kernel): per (tile, Gaussian) instance the seven geometry sums of
+// dL_ddepth's dL_dalpha chain are ADDED to g.grad_rec slots 3..9 (GRAD_REC_*: unscaled, float atomics -- the record must be clear or hold the
+// image pass's sums of the same frame) and sum(w dL_ddepth) to dL_dvalues[id], which must arrive zeroed; tiles in img.order_bwd's order over their
+// first tile_last entries.  values == nullptr: the scalar is |means3D[id] - campos|
+hipError_t launch_render_depth_backward(int W, int H, int gx, int gy, const ImageState& img, const BinningState& b, const GeometryState& g,
+                                        const float* subpixel_offset, const float* dL_ddepth, const float* values, const float* means3D,
+                                        const float* campos, float* dL_dvalues, bool exact, hipStream_t stream);
+// distance mode, behind the per-Gaussian backward kernel: dL_dmean3D[g] += dL_dvalues[g] * (means3D[g] - campos) / |means3D[g] - campos| (0 at distance 0)
+hipError_t launch_depth_distance_fold(int P, const float* means3D, const float* campos, const float* dL_dvalues, float* dL_dmean3D, hipStream_t stream);
 
 struct BwdParams {
     int P, D, M, W, H;

@@ -64,7 +64,7 @@ def binding_name() -> str:
 
 
 from ._abi import (_ALLOC_FN, _vp, _i, _f, _ShTone, _SecondImage, _RawGaussians, _RecolorParent, _CallOptions, _ForwardArgs,  # noqa: E402
-                    _BackwardArgs, _ProjectArgs, _DepthArgs)   # (pure ctypes)
+                    _BackwardArgs, _ProjectArgs, _DepthArgs, _DepthGrad)   # (pure ctypes)
 
 _lib.wg_rasterize_forward.restype = _i
 _lib.wg_rasterize_forward.argtypes = [_ALLOC_FN, _vp, _ALLOC_FN, _vp, _ALLOC_FN, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp,
@@ -466,6 +466,36 @@ def colour_only_refused(has_sh, toned, second, raw, sh_second, opts) -> bool:
     return bool(has_sh or toned or second or raw or sh_second or opts[1])
 
 
+# The depth pass's gradient (wg_depth_grad): one more walk of the frame's backward call that adds into the ATOMIC gradient record, so it is refused
+# wherever there is no such record (the library returns WG_ERR_INVALID_ARGUMENT for the same calls) -- by the operator at forward time, by
+# rasterize_gaussians_backward in front of both bindings, with this one message.
+DEPTH_GRAD_MSG = ("depth_grad adds the depth loss's gradient into the frame's gradient record: it cannot be combined with colour_gradients_only, "
+                  "deterministic_backward = 1, grad_record = 0 or binning_capacity")
+DEPTH_GRAD_BLOCK_MSG = "depth is (dL_ddepth, source): the depth cotangent [H, W] and the frame's return_depth source"
+DEPTH_GRAD_COTANGENT_MSG = "dL_ddepth must be a float32 tensor of H * W elements on the frame's HIP device"
+
+
+def depth_grad_refused(colour_only, opts, fixed_capacity=False) -> bool:
+    """What a depth gradient cannot be combined with: the colour-only backward pass, deterministic_backward = 1, grad_record = 0 (opts = the
+    resolved per-call options) and, at forward time, binning_capacity (refused for depth already)."""
+    return bool(colour_only or opts[1] or not opts[2] or fixed_capacity)
+
+
+def _check_depth_grad_arguments(depth, P, dL_dout_color):
+    """What rasterize_gaussians_backward refuses of its `depth` block, after the mode check in front of both bindings.  The compiled binding
+    makes the same checks in the same order with the same messages (csrc/torch_binding.cpp: DepthGrad)."""
+    if not isinstance(depth, (tuple, list)) or len(depth) != 2:
+        raise RuntimeError(DEPTH_GRAD_BLOCK_MSG)
+    dL_ddepth, source = depth
+    device = dL_dout_color.device
+    if (not isinstance(dL_ddepth, torch.Tensor) or dL_ddepth.dtype != torch.float32 or dL_ddepth.numel() * 3 != dL_dout_color.numel()
+            or dL_ddepth.device != device):
+        raise RuntimeError(DEPTH_GRAD_COTANGENT_MSG)
+    check_depth_source(source, P)
+    if isinstance(source, torch.Tensor) and (not source.is_cuda or source.device != device):
+        raise RuntimeError(DEPTH_SOURCE_MSG)
+
+
 def _fill(a, device, P, degree, M, H, W, debug, scale_modifier, tan_fovx, tan_fovy, kernel_size, **tensors):
     """The fields wg_forward_args and wg_backward_args share; every other pointer field by name (None or zero-sized = NULL)."""
     a.struct_size = C.sizeof(a)
@@ -598,8 +628,13 @@ def _forward_ctypes(background, means3D, colors, opacity, scales, rotations, sca
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, kernel_size, subpixel_offset, dL_dout_color, sh,
                                  degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, sh_tone=None, dL_dout_color2=None, raw=None,
-                                 sh_second=None, options=None, colour_gradients_only=None, want=None):
+                                 sh_second=None, options=None, colour_gradients_only=None, want=None, depth=None):
     """The reference's `rasterize_gaussians_backward` (rasterize_points.h:42-66) -> the eight tensors, plus by keyword:
+    depth = (dL_ddepth [H, W], source): the cotangent of the frame's depth output (render_depth) and its source -- "distance" or the float32 [P]
+      tensor of scalars.  One more per-tile walk adds the depth loss's gradient into the gradient record (wg_depth_grad), so the geometry
+      gradients returned are those of the image loss plus the depth loss; in distance mode dL_dmeans3D also carries the direct term.  The result
+      ends with one more tensor, dL_dvalues [P] (the gradient of the scalars).  Needs the atomic gradient record: refused with
+      colour_gradients_only, deterministic_backward = 1 and grad_record = 0.  None: today's call, nothing new runs.
     want = (dL_dcolors, dL_dcov3D) booleans (None = both): whether the caller reads them.  One it does not want comes back as None wherever the
       library treats it as an intermediate (dL_dcolors with SH colours and the gradient record, dL_dcov3D without cov3D_precomp): it is then
       neither allocated nor stored (wg_backward_args: NULL).  The autograd function passes its needs_input_grad.
@@ -624,8 +659,10 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         alive = {t.ident for t in threading.enumerate()}
         for ident in [i for i in states if i not in alive]:
             states.pop(ident, None)
+    if depth is not None and depth_grad_refused(colour_only, opts):   # the mode checks, in front of both bindings
+        raise RuntimeError(DEPTH_GRAD_MSG)
     if colour_only and colour_only_refused(sh.numel() != 0, sh_tone is not None, dL_dout_color2 is not None, raw is not None,
-                                           sh_second is not None, opts):   # the mode checks, in front of both bindings
+                                           sh_second is not None, opts):
         raise RuntimeError(COLOUR_ONLY_MSG)
     if sh_second is not None and dL_dout_color2 is None:
         raise RuntimeError("sh_second needs the second image's cotangent (dL_dout_color2)")
@@ -644,21 +681,28 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         _check_backward_arguments(means3D, radii, colors, scales, rotations, cov3D_precomp, sh, dL_dout_color, None, None, None, None)
         return _backward_colour_ctypes(background, means3D, colors, subpixel_offset, dL_dout_color, geomBuffer, R, binningBuffer, imageBuffer, debug, opts,
                                        _COLOUR_MODE_ABI[colour_only])
+    if _torch_ext is not None and depth is not None:
+        return _torch_ext.rasterize_gaussians_backward_depth(background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
+                                                             viewmatrix, projmatrix, float(tan_fovx), float(tan_fovy), float(kernel_size), subpixel_offset,
+                                                             dL_dout_color, sh, int(degree), campos, geomBuffer, int(R), binningBuffer, imageBuffer,
+                                                             bool(debug), sh_tone, dL_dout_color2, raw, sh_second, opts, want_colors, want_cov3D, depth)
     if _torch_ext is not None:
         return _torch_ext.rasterize_gaussians_backward_ex(background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
                                                           viewmatrix, projmatrix, float(tan_fovx), float(tan_fovy), float(kernel_size), subpixel_offset,
                                                           dL_dout_color, sh, int(degree), campos, geomBuffer, int(R), binningBuffer, imageBuffer,
                                                           bool(debug), sh_tone, dL_dout_color2, raw, sh_second, opts, want_colors, want_cov3D)
     _check_backward_arguments(means3D, radii, colors, scales, rotations, cov3D_precomp, sh, dL_dout_color, sh_tone, dL_dout_color2, raw, sh_second)
+    if depth is not None:
+        _check_depth_grad_arguments(depth, means3D.size(0), dL_dout_color)
     return _backward_ctypes(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
                             tan_fovy, kernel_size, subpixel_offset, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug,
-                            sh_tone, dL_dout_color2, raw, sh_second, opts, want_colors, want_cov3D)
+                            sh_tone, dL_dout_color2, raw, sh_second, opts, want_colors, want_cov3D, depth)
 
 
 def _backward_ctypes(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                      kernel_size, subpixel_offset, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, sh_tone,
-                     dL_dout_color2, raw, sh_second, opts, want_colors=True, want_cov3D=True):
-    """The checked backward call through ctypes -> the reference's eight, + what the optional blocks add."""
+                     dL_dout_color2, raw, sh_second, opts, want_colors=True, want_cov3D=True, depth=None):
+    """The checked backward call through ctypes -> the reference's eight, + what the optional blocks add (+ dL_dvalues [P] last with `depth`)."""
     device, P, H, W = means3D.device, means3D.size(0), dL_dout_color.size(1), dL_dout_color.size(2)
     sh = _f32(sh, device)
     M = sh.size(1) if sh.numel() != 0 else 0
@@ -683,6 +727,7 @@ def _backward_ctypes(background, means3D, radii, colors, scales, rotations, scal
     dL_dscales, dL_drotations = alloc_sr((P, 3), **f), alloc_sr((P, 4), **f)
     dL_dcolors2 = alloc((P, 3), **f) if dual else None
     tone_grads, tone2_grads = (None if t is None else tuple(None if v is None else alloc((P, 3), **f) for v in t[:2]) for t in (sh_tone, sh_second))
+    dL_dvalues = None if depth is None else alloc((P,), **f)   # (the library fills it)
     if P != 0:
         means3D, background, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, subpixel_offset, dL_dout_color = _f32s(
             device, means3D, background, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, subpixel_offset, dL_dout_color)
@@ -700,15 +745,23 @@ def _backward_ctypes(background, means3D, radii, colors, scales, rotations, scal
                               tone2=None if sh_second is None else _tone_block(sh_second, device, P, tone2_grads),
                               second=None if dL_dout_color2 is None else _second_block(device, dL_dpix2=dL_dout_color2, dL_dcolor2=dL_dcolors2),
                               raw=None if raw is None else _raw_block(device, *raw))
+        if depth is not None:   # wg_depth_grad: the cotangent, the scalars (NULL = distance: the call's means3D and campos) and their gradient
+            dL_ddepth, source = depth
+            dL_ddepth = dL_ddepth.contiguous()
+            values = None if isinstance(source, str) else source.contiguous()
+            block = _DepthGrad(C.sizeof(_DepthGrad), dL_ddepth.data_ptr(), None if values is None else values.data_ptr(), dL_dvalues.data_ptr())
+            keep += [dL_ddepth, values, block]
+            a.depth = C.pointer(block)
         with torch.cuda.device(device):
             status = _lib.wg_rasterize_backward_ex(C.byref(a))
         _check(status, "wg_rasterize_backward")
     out = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
+    last = () if depth is None else (dL_dvalues,)
     if sh_second is not None:
-        return out + (tone_grads or (None, None)) + tone2_grads
+        return out + (tone_grads or (None, None)) + tone2_grads + last
     if dual:
-        return out + (dL_dcolors2,)
-    return out if sh_tone is None else out + tone_grads   # (raw-parameter mode: same tuple, slots 2, 6, 7 are gradients of the raw parameters)
+        return out + (dL_dcolors2,) + last
+    return (out if sh_tone is None else out + tone_grads) + last   # (raw-parameter mode: same tuple, slots 2, 6, 7 are gradients of the raw parameters)
 
 
 def _backward_colour_ctypes(background, means3D, colors, subpixel_offset, dL_dout_color, geomBuffer, R, binningBuffer, imageBuffer, debug, opts, mode=1):
@@ -976,7 +1029,7 @@ def version() -> str:
 
 # ----------------------------------------------------------------------------------------------------------
 # Per-stage HIP-event timing (wg_profile_* in wg_rasterizer.h); used by bench.py for the roofline object.
-STAGE_COUNT = 10  # WG_STAGE_COUNT (include/wg_rasterizer.h)
+STAGE_COUNT = 11  # WG_STAGE_COUNT (include/wg_rasterizer.h)
 
 
 class _StageTimes(C.Structure):

@@ -79,7 +79,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                 sh_mul=None, sh_offset=None, sh_pre_clamp_max=None, sh_post_clamp_max=None, binning_capacity=None, colors_precomp2=None,
                 filter_3D=None, sh_second=False, sh_mul2=None, sh_offset2=None, sh_pre_clamp_max2=None, sh_post_clamp_max2=None, call_options=None,
-                colour_gradients_only=None, grad_mode=True, return_depth=None):
+                colour_gradients_only=None, grad_mode=True, depth_grad=False, return_depth=None):
         rs = raster_settings
         native_args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                        rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.kernel_size, rs.subpixel_offset,
@@ -110,8 +110,14 @@ class _RasterizeGaussians(torch.autograd.Function):
         # the depth pass over the finished frame (wg_render_depth): refused now, before anything is rendered, where it cannot be served
         if return_depth is not None:
             _C.check_depth_source(return_depth, means3D.shape[0])
+            # depth_grad: the frame's backward call adds the depth loss's gradient into its gradient record (wg_depth_grad) -- refused now where
+            # there is no such record, not in the middle of a backward pass
+            if depth_grad and _C.depth_grad_refused(ctx.colour_only, ctx.call_options, binning_capacity is not None):
+                raise Exception(_C.DEPTH_GRAD_MSG)
             if binning_capacity is not None:
                 raise Exception(_C.DEPTH_CAPACITY_MSG)
+        elif depth_grad:
+            raise Exception("depth_grad=True is the gradient of the depth output: pass return_depth too")
         if binning_capacity is not None:   # no host rendezvous (wg_forward_args::binning_capacity), capturable in a hipGraph
             extra["binning_capacity"] = int(binning_capacity)
         # a second set of precomputed colours composited in the same walk (wg_second_image)
@@ -154,6 +160,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                 accumulation = _accumulation_from_image_state(img_buf, rs.image_height, rs.image_width)
         out = (color, radii, accumulation, color2) if ctx.dual or ctx.sh_second is not None else (color, radii, accumulation)
         ctx.depth = return_depth is not None
+        ctx.depth_grad = ctx.depth and bool(depth_grad)
+        ctx.depth_source = None
         if ctx.depth:
             # one more walk over the frame just finished, reading its buffers only (whichever call served it: a full one or, with geometry
             # reuse, a recolouring): the image stays differentiable as before, depth takes no gradient
@@ -161,14 +169,19 @@ class _RasterizeGaussians(torch.autograd.Function):
                                  (geom_buf, binning_buf, img_buf, num_rendered, means3D.shape[0], rs.image_height, rs.image_width,
                                   return_depth.detach() if isinstance(return_depth, torch.Tensor) else return_depth, means3D.detach(), rs.campos,
                                   rs.subpixel_offset), rs.debug, "snapshot_depth.dump", "the depth pass")
-            ctx.mark_non_differentiable(depth)
+            if ctx.depth_grad:   # the scalars go to the backward call as the forward pass read them ("distance": the call's means3D and campos)
+                ctx.depth_source = return_depth.detach() if isinstance(return_depth, torch.Tensor) else return_depth
+            else:
+                ctx.mark_non_differentiable(depth)
             out += (depth,)
         return out
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, _grad_accumulation, grad_out_color2=None, _grad_depth=None):
-        if ctx.depth and ctx.sh_second is None and not ctx.dual:   # (color, radii, accumulation, depth): the fourth cotangent is depth's, always None
-            grad_out_color2 = None
+    def backward(ctx, grad_out_color, _grad_radii, _grad_accumulation, grad_out_color2=None, grad_depth=None):
+        if ctx.depth and ctx.sh_second is None and not ctx.dual:   # (color, radii, accumulation, depth): the fourth cotangent is depth's
+            grad_depth, grad_out_color2 = grad_out_color2, None
+        if not ctx.depth_grad:   # (depth was marked non-differentiable: its cotangent is always None)
+            grad_depth = None
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf, binning_buf, img_buf = ctx.saved_tensors[:10]
         zeros = lambda: torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
@@ -180,7 +193,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         extra = dict(options=ctx.call_options, colour_gradients_only=ctx.colour_only)   # the frame's forward call's
         if ctx.colour_only:   # dL_dcolors and nothing else: the geometry inputs' .grad stay as they were
             g_colors = _call_native(lambda *a: _C.rasterize_gaussians_backward(*a, **extra), native_args, rs.debug, "snapshot_bw.dump", "backward")[1]
-            return (None, None, None, g_colors) + (None,) * 21
+            return (None, None, None, g_colors) + (None,) * 22
         # dL_dcolors / dL_dcov3D are intermediates of a plain SH + scales/rotations call: wanted only where the input takes a gradient (what is not
         # wanted comes back as None, neither allocated nor stored)
         extra["want"] = (ctx.needs_input_grad[3], ctx.needs_input_grad[7])
@@ -192,6 +205,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             extra["dL_dout_color2"] = zeros() if grad_out_color2 is None else grad_out_color2   # (None: the second image took no gradient)
         if ctx.sh_second is not None:
             extra["sh_second"] = ctx.sh_second
+        if grad_depth is not None:   # a loss on depth: one more walk adds its gradient into the record (None: today's call, no walk)
+            extra["depth"] = (grad_depth, ctx.depth_source)
         res = _call_native(lambda *a: _C.rasterize_gaussians_backward(*a, **extra), native_args, rs.debug, "snapshot_bw.dump", "backward")
         (g_means2D, g_colors, g_opacities, g_means3D, g_cov3Ds, g_sh, g_scales, g_rotations) = res[:8]
         g_mul = g_offset = g_colors2 = g_mul2 = g_offset2 = None
@@ -205,20 +220,24 @@ class _RasterizeGaussians(torch.autograd.Function):
             g_colors2 = res[8]
         elif ctx.sh_tone is not None:
             g_mul, g_offset = shaped(res[8], ctx.sh_tone[0]), shaped(res[9], ctx.sh_tone[1])
+        # the scalars' gradient, where return_depth was a tensor that takes one (its place among forward()'s inputs: the last)
+        g_values = None
+        if grad_depth is not None and isinstance(ctx.depth_source, torch.Tensor) and ctx.needs_input_grad[25]:
+            g_values = res[-1].view(ctx.depth_source.shape)
         # order of forward()'s inputs; None for raster_settings, the clamp constants and the options
         return (g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3Ds, None, g_mul, g_offset, None, None, None, g_colors2, None,
-                None, g_mul2, g_offset2, None, None, None, None, None, None)
+                None, g_mul2, g_offset2, None, None, None, None, None, None, g_values)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                         sh_mul=None, sh_offset=None, sh_pre_clamp_max=None, sh_post_clamp_max=None, binning_capacity=None, colors_precomp2=None,
                         filter_3D=None, sh_second=False, sh_mul2=None, sh_offset2=None, sh_pre_clamp_max2=None, sh_post_clamp_max2=None, call_options=None,
-                        *, colour_gradients_only=None, return_depth=None):
+                        *, colour_gradients_only=None, return_depth=None, depth_grad=False):
     _C._colour_mode(colour_gradients_only)   # (an unknown string: ValueError, before anything touches the device)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                      raster_settings, sh_mul, sh_offset, sh_pre_clamp_max, sh_post_clamp_max, binning_capacity, colors_precomp2,
                                      filter_3D, sh_second, sh_mul2, sh_offset2, sh_pre_clamp_max2, sh_post_clamp_max2, call_options,
-                                     colour_gradients_only, torch.is_grad_enabled(), return_depth)
+                                     colour_gradients_only, torch.is_grad_enabled(), bool(depth_grad), return_depth)
 
 
 class GaussianRasterizer(nn.Module):
@@ -264,16 +283,28 @@ class GaussianRasterizer(nn.Module):
                 sh_offset2: Optional[torch.Tensor] = None, sh_pre_clamp_max2: Optional[float] = None,
                 sh_post_clamp_max2: Optional[float] = None, exact_compositing: Optional[bool] = None,
                 deterministic_backward: Optional[bool] = None, grad_record: Optional[bool] = None,
-                colour_gradients_only=None, return_depth=None):
-        """`return_depth=` (keyword-only, beyond the reference): `"distance"` or a float32 [P] device tensor of per-Gaussian scalars.  The call
+                colour_gradients_only=None, return_depth=None, depth_grad: bool = False):
+        """`depth_grad=True` (keyword-only, beyond the reference; with `return_depth=`): `depth` is DIFFERENTIABLE -- with respect to the call's
+        geometry inputs (`means3D`, `means2D` as the carrier of the screen-space gradient, `opacities`, `scales` / `rotations` or `cov3D_precomp`;
+        with `filter_3D=` the RAW parameters), to a `return_depth` tensor that requires grad, and in `"distance"` mode to `means3D` through
+        v = |means3D - campos| as well (`campos` is a settings field and takes none).  A loss on depth then costs ONE more per-tile walk in the
+        frame's backward call, which adds its sums into the gradient record the image walk fills before the per-Gaussian kernel reads it
+        (wg_depth_grad) -- in place of a second three-channel call with the distances as colours and its whole backward pass.  The gradients are
+        those two calls would give added up; `means2D.grad[:, 2]`, the densification statistic, accumulates |q_depth| beside |q_image| as they
+        would.  A backward pass in which depth took no gradient is the call without the keyword: no walk is launched.  A backward pass with only
+        a depth cotangent runs the image walk on a zero image cotangent.  Refused at forward time with `colour_gradients_only`,
+        `deterministic_backward=1`, `grad_record=0` and `binning_capacity` (it needs the atomic gradient record), and without `return_depth`.
+        False (the default): depth takes no gradient, as before.
+
+        `return_depth=` (keyword-only, beyond the reference): `"distance"` or a float32 [P] device tensor of per-Gaussian scalars.  The call
         then returns what it returns otherwise PLUS, as its LAST output, `depth` ([H, W] float32): the scalar composited over the frame just
         rendered like a colour channel -- sum over the blended (pixel, Gaussian) pairs of v * alpha * T, with the frame's own decisions, no
         background term and no division by the accumulation.  `"distance"` is v = |means3D - campos|: the image WildGaussians' depth render
         (method.py:1621-1631: `torch.norm(means3D - camera_center[None], dim=-1)` repeated to three channels through a second rasterizer call
         over a zero background) keeps one channel of -- here one more single-channel walk over the finished frame's lists instead of a second
         projection, binning, sort and three-channel walk (wg_render_depth).  A tensor gives any scalar attribute (view-space z, a label
-        weight, ...) the same treatment, with the bits of one channel of `colors_precomp=v[:, None].repeat(1, 3)`.  Depth takes no gradient; the
-        colour outputs stay differentiable exactly as without it.  Works under `torch.no_grad()`, with every colour source of the call and on a
+        weight, ...) the same treatment, with the bits of one channel of `colors_precomp=v[:, None].repeat(1, 3)`.  Depth takes no gradient
+        (unless `depth_grad=True`, above); the colour outputs stay differentiable exactly as without it.  Works under `torch.no_grad()`, with every colour source of the call and on a
         frame served by geometry reuse; refused with `binning_capacity`.  None (the default): outputs and gradients are what they were.
 
         `colour_gradients_only=True` (keyword-only, beyond the reference; with `colors_precomp`): the frame's backward pass computes the
@@ -339,4 +370,4 @@ class GaussianRasterizer(nn.Module):
             sh_second, sh_mul2, sh_offset2, sh_pre_clamp_max2, sh_post_clamp_max2,
             None if exact_compositing is None and deterministic_backward is None and grad_record is None else
             dict(exact_compositing=exact_compositing, deterministic_backward=deterministic_backward, grad_record=grad_record),
-            colour_gradients_only=colour_gradients_only, return_depth=return_depth)
+            colour_gradients_only=colour_gradients_only, return_depth=return_depth, depth_grad=depth_grad)

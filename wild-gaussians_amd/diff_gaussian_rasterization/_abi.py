@@ -38,6 +38,10 @@ class _ForwardArgs(C.Structure):  # wg_forward_args
                  ("options", C.POINTER(_CallOptions))])
 
 
+class _DepthGrad(C.Structure):  # wg_depth_grad
+    _fields_ = [("struct_size", C.c_size_t), ("dL_ddepth", _vp), ("values", _vp), ("dL_dvalues", _vp)]
+
+
 class _BackwardArgs(C.Structure):  # wg_backward_args
     _fields_ = ([("struct_size", C.c_size_t)] + [(n, _i) for n in ("P", "D", "M", "R", "width", "height", "debug")] +
                 [(n, _f) for n in ("scale_modifier", "tan_fovx", "tan_fovy", "kernel_size")] +
@@ -45,7 +49,8 @@ class _BackwardArgs(C.Structure):  # wg_backward_args
                                     "campos", "subpixel_offset", "radii", "geom_buffer", "binning_buffer", "image_buffer", "dL_dpix", "dL_dmean2D",
                                     "dL_dconic", "dL_dopacity", "dL_dcolor", "dL_dmean3D", "dL_dcov3D", "dL_dsh", "dL_dscale", "dL_drot", "stream")] +
                 [("tone", C.POINTER(_ShTone)), ("tone2", C.POINTER(_ShTone)), ("sh_second", _i), ("second", C.POINTER(_SecondImage)),
-                 ("raw", C.POINTER(_RawGaussians)), ("options", C.POINTER(_CallOptions)), ("colour_gradients_only", _i)])
+                 ("raw", C.POINTER(_RawGaussians)), ("options", C.POINTER(_CallOptions)), ("colour_gradients_only", _i),
+                 ("depth", C.POINTER(_DepthGrad))])   # (appended: sizeof 320 -> 328)
 
 
 class _ProjectArgs(C.Structure):  # wg_project_args
