@@ -284,7 +284,7 @@ int wg_view_image(char* image_buffer, int width, int height, wg_image_view* out)
 /* ---- per-stage timing with HIP events on the caller's stream (bench.py's roofline): enable, run, read (synchronises) ---- */
 enum { WG_STAGE_PREPROCESS = 0, WG_STAGE_SCAN, WG_STAGE_DUPLICATE_KEYS, WG_STAGE_SORT, WG_STAGE_TILE_RANGES,
        WG_STAGE_RENDER_FORWARD, WG_STAGE_RENDER_BACKWARD, WG_STAGE_PREPROCESS_BACKWARD, WG_STAGE_RENDER_FIXUP, WG_STAGE_RENDER_DEPTH, WG_STAGE_RENDER_DEPTH_BACKWARD,
-       WG_STAGE_COUNT };
+       WG_STAGE_RENDER_CONTRIBUTIONS, WG_STAGE_COUNT };
 typedef struct wg_stage_times {
     double total_ms[WG_STAGE_COUNT];
     long long launches[WG_STAGE_COUNT];
@@ -362,6 +362,42 @@ typedef struct wg_depth_args {
     void* stream;
 } wg_depth_args;
 int wg_render_depth(const wg_depth_args* args);
+
+/* ---- the contribution pass: what each Gaussian contributed to a FINISHED frame ----
+ * Over the (pixel, Gaussian) pairs the frame's forward call blended (the depth pass's predicate), with w = alpha * T the forward call's own
+ * blend weight, bit for bit:
+ *   max_weight[g]     the largest w, combined by an unsigned-integer atomic max on the float's bit pattern (w > 0: the bit order is the
+ *                     value order);
+ *   hits[g]           the number of pairs, a 64-bit integer atomic add;
+ *   weight_sum_q32[g] the sum of (unsigned long long)(w * 2^32), each term truncated (so within 2^-32 of w), a 64-bit integer atomic add:
+ *                     the summed weight is weight_sum_q32 * 2^-32.
+ * Integer atomics commute exactly: two calls give the same bits whatever order the tiles ran in.  A NaN weight counts as a hit, adds 0 to the
+ * sum and makes max_weight NaN (its bit pattern is above every finite weight's).  Each of the three outputs may be NULL (not all three).
+ *   pixel_mask: float[H*W] or NULL; a pixel whose entry compares equal to 0.0f (-0.0f too) takes no part.
+ *   accumulate: 0 = the (non-NULL) arrays are zero-filled on `stream` under this call first; 1 = the pass combines into what an earlier call
+ *     or a zero fill left (a sweep over many cameras).  max_weight must not hold negative values or the combination is meaningless.
+ *   geom_buffer / binning_buffer / image_buffer, R, subpixel_offset, options: the frame's, as wg_render_depth takes them;
+ *     options->exact_compositing must be the frame's (WG_ERR_INVALID_ARGUMENT otherwise).
+ * One launch on `stream` (behind up to three memsets with accumulate = 0) over each tile's list up to tile_last, at most three atomics per
+ * (tile, Gaussian).  The three buffers are only READ.  No scratch, no allocator, no host wait -- but for a frame of the deferred forward, whose
+ * verdict is read first (WG_ERR_SPECULATION: nothing is written).  P = 0 or R = 0: WG_OK after the optional zero fill.
+ * WG_ERR_INVALID_ARGUMENT, before any device work: struct_size smaller than the struct, P < 0, R < 0, width or height <= 0, all three outputs
+ * NULL, accumulate not 0 or 1, with P > 0 a NULL buffer.  Fields are only ever appended. */
+typedef struct wg_contrib_args {
+    size_t struct_size;   /* the CALLER's sizeof(wg_contrib_args) */
+    int P, R, width, height;
+    char *geom_buffer, *binning_buffer, *image_buffer;
+    const float* subpixel_offset;        /* the frame's float[H*W*2], or NULL */
+    const float* pixel_mask;             /* [H*W] or NULL */
+    const wg_call_options* options;      /* NULL = WG_CALL_OPTIONS_DEFAULT */
+    float* max_weight;                   /* [P] or NULL */
+    unsigned long long* hits;            /* [P] or NULL */
+    unsigned long long* weight_sum_q32;  /* [P] or NULL */
+    int accumulate;                      /* 0: zero-fill first; 1: combine */
+    int debug;                           /* 1: synchronise behind the launch and report (as the other calls' debug) */
+    void* stream;
+} wg_contrib_args;
+int wg_render_contributions(const wg_contrib_args* args);
 
 #ifdef __cplusplus
 }

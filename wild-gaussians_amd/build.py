@@ -39,6 +39,9 @@ SOURCES = {
                                                  # render_fwd.hip's flags, so that the sum has the forward kernel's instruction and its bits
     "depth/depth_bwd.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],   # the depth pass's gradient (wg_depth_grad): render_bwd.hip's walk with one
                                                                             # channel, adding into the same gradient record; render_bwd.hip's flags
+    "contrib/contrib.hip": ["-fno-slp-vectorize"],   # the contribution pass (wg_render_contributions): the forward walk over a finished frame
+                                                     # with per-Gaussian integer reductions; render_fwd.hip's flags, so that alpha * T and T
+                                                     # come out of the forward kernel's instructions
     "binning.hip": ["-fno-slp-vectorize"],
     "render_fwd.hip": ["-fno-slp-vectorize"],
     "render_bwd.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],

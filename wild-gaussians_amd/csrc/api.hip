@@ -314,7 +314,8 @@ struct StageScope {
 const char* stage_label(int stage) {
     static const char* names[WG_STAGE_COUNT] = {"wg:K1 preprocess", "wg:K2-K3 scan", "wg:K4 duplicate_keys", "wg:K5 sort", "wg:K6-K7 tile_ranges",
                                                 "wg:K8 render_forward", "wg:K9 render_backward", "wg:K10-K11 preprocess_backward",
-                                                "wg:K8 render_fixup", "wg:K8d render_depth", "wg:K9d render_depth_backward"};
+                                                "wg:K8 render_fixup", "wg:K8d render_depth", "wg:K9d render_depth_backward",
+                                                "wg:K8c render_contributions"};
     return (stage >= 0 && stage < WG_STAGE_COUNT) ? names[stage] : "wg:?";
 }
 
@@ -658,6 +659,7 @@ std::atomic<uint64_t> g_row_frames{0}, g_row_backwards{0};
 std::atomic<uint64_t> g_clean_frames{0}, g_clean_backwards{0};
 // ... backward calls whose per-tile launch zeroed dL_dsh for a per-Gaussian kernel that stored the touched rows only (wg_common.h: WG_SH_GRAD_SKIP)
 std::atomic<uint64_t> g_sh_skip_backwards{0};
+std::atomic<uint64_t> g_contribution_calls{0};     // wg_render_contributions calls that launched the walk (R > 0); read-only option "contribution_calls"
 std::atomic<uint64_t> g_depth_grad_backwards{0};   // backward calls that ran the depth cotangent's walk (wg_depth_grad); read-only option "depth_grad_calls"
 std::mutex g_mode_mu;
 FrameMode g_modes[64];
@@ -1522,6 +1524,52 @@ int wg_render_depth(const wg_depth_args* args) {
     return WG_OK;
 }
 
+// The contribution pass (contrib/contrib.hip: render_contrib_kernel): one launch over the finished frame's lists, modelled on wg_render_depth
+// above.  The frame's three buffers are only read; the three caller-owned arrays are combined into with integer atomics.
+int wg_render_contributions(const wg_contrib_args* args) {
+    if (!args || args->struct_size < sizeof(wg_contrib_args)) return WG_ERR_INVALID_ARGUMENT;
+    const wg_contrib_args& a = *args;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(a.stream);
+    const int P = a.P, R = a.R, width = a.width, height = a.height, debug = a.debug;
+    const wg::Options opt = call_options_snapshot(a.options);
+    if (a.image_buffer != nullptr && P > 0) {   // the frame was composited with the other arithmetic: its stored decisions are not this call's
+        const int fwd_mode = remembered_mode(a.image_buffer);
+        if (fwd_mode >= 0 && fwd_mode != (opt.exact_compositing ? 1 : 0)) return WG_ERR_INVALID_ARGUMENT;
+    }
+    if (P < 0 || R < 0 || width <= 0 || height <= 0) return WG_ERR_INVALID_ARGUMENT;
+    if (!a.max_weight && !a.hits && !a.weight_sum_q32) return WG_ERR_INVALID_ARGUMENT;
+    if (a.accumulate != 0 && a.accumulate != 1) return WG_ERR_INVALID_ARGUMENT;
+    if (P > 0 && (!a.geom_buffer || !a.binning_buffer || !a.image_buffer)) return WG_ERR_INVALID_ARGUMENT;
+    if (a.image_buffer != nullptr) {   // a deferred forward call's verdict, as in the backward passes
+        const int verdict = check_ticket(image_key(a.image_buffer), stream);
+        if (verdict != WG_OK) return verdict;
+    }
+    if (P == 0) return WG_OK;   // nothing to fill, nothing to walk
+    StageScope scope_(WG_STAGE_RENDER_CONTRIBUTIONS, stream);
+    if (a.accumulate == 0) {
+        hipError_t e = hipSuccess;
+        if (a.max_weight) e = hipMemsetAsync(a.max_weight, 0, (size_t)P * sizeof(float), stream);
+        if (e == hipSuccess && a.hits) e = hipMemsetAsync(a.hits, 0, (size_t)P * sizeof(unsigned long long), stream);
+        if (e == hipSuccess && a.weight_sum_q32) e = hipMemsetAsync(a.weight_sum_q32, 0, (size_t)P * sizeof(unsigned long long), stream);
+        if (e != hipSuccess) return hip_fail(e, "contributions memset");
+    }
+    if (R == 0) return WG_OK;   // no lists to walk: no pair was blended
+    const int gx = (width + wg::TILE_X - 1) / wg::TILE_X, gy = (height + wg::TILE_Y - 1) / wg::TILE_Y;
+    char *geom_buffer = a.geom_buffer, *binning_buffer = a.binning_buffer, *image_buffer = a.image_buffer;   // (fromChunk advances its argument)
+    wg::GeometryState geom = wg::GeometryState::fromChunk(geom_buffer, (size_t)P, false);
+    wg::BinningState bin = wg::BinningState::fromChunk(binning_buffer, (size_t)R, false);  // only point_list is used
+    wg::ImageState img = wg::ImageState::fromChunk(image_buffer, (size_t)width * height, (size_t)gx * gy);
+    g_contribution_calls.fetch_add(1, std::memory_order_relaxed);
+    hipError_t e = wg::launch_render_contrib(width, height, gx, gy, img, bin, geom, a.subpixel_offset, a.pixel_mask, a.max_weight, a.hits,
+                                             a.weight_sum_q32, opt.exact_compositing != 0, stream);
+    if (e != hipSuccess) return hip_fail(e, "render_contributions");
+    if (debug) {
+        e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) return hip_fail(e, "render_contributions");
+    }
+    return WG_OK;
+}
+
 int wg_view_geometry(char* geom_buffer, int P, wg_geometry_view* out) {
     if (!geom_buffer || !out || P < 0) return WG_ERR_INVALID_ARGUMENT;
     wg::GeometryState g = wg::GeometryState::fromChunk(geom_buffer, (size_t)P, false);
@@ -1664,6 +1712,7 @@ int wg_get_option(const char* name) {
     // ... backward calls whose per-tile launch zeroed dL_dsh and whose per-Gaussian kernel stored the touched rows only
     if (std::strcmp(name, "sh_grad_skip_calls") == 0) return (int)std::min<uint64_t>(g_sh_skip_backwards.load(std::memory_order_relaxed), 0x7fffffffu);
     if (std::strcmp(name, "depth_grad_calls") == 0) return (int)std::min<uint64_t>(g_depth_grad_backwards.load(std::memory_order_relaxed), 0x7fffffffu);
+    if (std::strcmp(name, "contribution_calls") == 0) return (int)std::min<uint64_t>(g_contribution_calls.load(std::memory_order_relaxed), 0x7fffffffu);
     const OptionRow* r = find_option(name);
     return r ? r->get(options_snapshot()) : -1;
 }
@@ -1703,7 +1752,7 @@ int wg_profile_read(wg_stage_times* out) {
 const char* wg_stage_name(int stage) {
     static const char* names[WG_STAGE_COUNT] = {"preprocess", "scan", "duplicate_keys", "sort", "tile_ranges",
                                                 "render_forward", "render_backward", "preprocess_backward", "render_fixup", "render_depth",
-                                                "render_depth_backward"};
+                                                "render_depth_backward", "render_contributions"};
     return (stage >= 0 && stage < WG_STAGE_COUNT) ? names[stage] : "?";
 }
 

@@ -508,6 +508,65 @@ torch::Tensor RenderDepth(const torch::Tensor& geomBuffer, const torch::Tensor& 
     return depth;
 }
 
+// The contribution pass (wg_render_contributions): per Gaussian the largest blend weight, the number of blended pairs and their fixed-point sum
+// over the finished frame these three buffers belong to, combined into the caller's [P] tensors (any may be None).
+// The checks of _C.py's _check_contrib_arguments, in its order, with its messages.
+void RenderContributions(const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const int R, const int P,
+                         const int image_height, const int image_width, const py::object& max_weight, const py::object& hits,
+                         const py::object& weight_sum_q32, const py::object& pixel_mask, const OptTensor& subpixel_offset,
+                         const std::tuple<int, int, int>& options, const bool accumulate, const bool debug) {
+    const auto dev = imageBuffer.device();
+    if (max_weight.is_none() && hits.is_none() && weight_sum_q32.is_none())
+        throw std::runtime_error("at least one of max_weight, hits and weight_sum_q32 must be given");
+    const auto output = [&](const py::object& o, const char* name, const torch::ScalarType dtype, const char* dname) {
+        torch::Tensor t;
+        if (o.is_none()) return t;
+        const std::string msg = std::string(name) + " must be a contiguous " + dname + " tensor of P elements on the frame's HIP device";
+        if (!THPVariable_Check(o.ptr())) throw std::runtime_error(msg);
+        t = o.cast<torch::Tensor>();
+        if (t.scalar_type() != dtype || t.numel() != P || !t.is_contiguous() || t.device() != dev) throw std::runtime_error(msg);
+        return t;
+    };
+    const torch::Tensor mw = output(max_weight, "max_weight", torch::kFloat32, "float32"), hi = output(hits, "hits", torch::kInt64, "int64"),
+                        ws = output(weight_sum_q32, "weight_sum_q32", torch::kInt64, "int64");
+    if (P < 0 || R < 0 || image_height <= 0 || image_width <= 0)
+        throw std::runtime_error("P and num_rendered must not be negative, image_height and image_width must be positive");
+    const int64_t N = (int64_t)image_height * image_width;
+    torch::Tensor mask;
+    if (!pixel_mask.is_none()) {
+        const char* mask_msg = "contribution_mask must be a float32 tensor of H * W elements on the frame's HIP device";
+        if (!THPVariable_Check(pixel_mask.ptr())) throw std::runtime_error(mask_msg);
+        mask = pixel_mask.cast<torch::Tensor>();
+        if (mask.scalar_type() != torch::kFloat32 || mask.numel() != N || mask.device() != dev) throw std::runtime_error(mask_msg);
+    }
+    if (subpixel_offset.has_value() && subpixel_offset->numel() != 0 &&
+        (subpixel_offset->scalar_type() != torch::kFloat32 || subpixel_offset->numel() != 2 * N || subpixel_offset->device() != dev))
+        throw std::runtime_error("subpixel_offset must be float32 with H * W * 2 elements on the frame's HIP device");
+    if (!(geomBuffer.is_cuda() && binningBuffer.is_cuda() && imageBuffer.is_cuda())) throw std::runtime_error("the frame's buffers must live on a HIP device");
+    if (P == 0) return;   // no Gaussian: nothing to fill, nothing to walk (an empty tensor has no address to hand to the library)
+
+    const c10::DeviceGuard guard(dev);
+    const auto mk = mask.defined() ? mask.contiguous() : torch::Tensor(), so = subpixel_offset.has_value() ? subpixel_offset->contiguous() : torch::Tensor();
+    const wg_call_options co = call_options(options);
+    wg_contrib_args a{};
+    a.struct_size = sizeof(a);
+    a.P = P; a.R = R; a.width = image_width; a.height = image_height; a.debug = debug;
+    a.geom_buffer = bytes_of(geomBuffer); a.binning_buffer = bytes_of(binningBuffer); a.image_buffer = bytes_of(imageBuffer);
+    a.subpixel_offset = ptr(so); a.pixel_mask = ptr(mk);
+    a.options = &co;
+    a.max_weight = mw.defined() ? mw.data_ptr<float>() : nullptr;
+    a.hits = hi.defined() ? reinterpret_cast<unsigned long long*>(hi.data_ptr<int64_t>()) : nullptr;
+    a.weight_sum_q32 = ws.defined() ? reinterpret_cast<unsigned long long*>(ws.data_ptr<int64_t>()) : nullptr;
+    a.accumulate = accumulate ? 1 : 0;
+    a.stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
+    int status;
+    {
+        py::gil_scoped_release nogil;
+        status = wg_render_contributions(&a);
+    }
+    check(status, "wg_render_contributions");
+}
+
 // ---- everything beyond the reference, by argument (the blocks of wg_forward_args / wg_backward_args) -------------------------------------
 // -> the reference's six, + the second image with colors2 / sh_second
 py::tuple RasterizeGaussiansEx(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors, const torch::Tensor& opacity,
@@ -617,6 +676,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {   // ext.cpp:15-19
     m.def("mark_visible", &markVisible);
     m.def("project_radii", &ProjectRadii);                                     // wg_project_radii: a frame's radii before it is rendered
     m.def("render_depth", &RenderDepth);                                       // wg_render_depth: a scalar per Gaussian composited over a finished frame
+    m.def("render_contributions", &RenderContributions);                       // wg_render_contributions: per-Gaussian contribution statistics of a finished frame
     m.def("rasterize_gaussians_ex", &RasterizeGaussiansEx);                    // + the blocks of wg_forward_args, + the forward_only hint
     m.def("rasterize_gaussians_ex", &RasterizeGaussiansExNoHint);              //   (overload without the hint)
     m.def("rasterize_gaussians_backward_ex", &RasterizeGaussiansBackwardEx);   // + the blocks of wg_backward_args, + which of dL_dcolors / dL_dcov3D the caller wants

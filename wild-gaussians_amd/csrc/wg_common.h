@@ -498,6 +498,12 @@ hipError_t launch_render_depth_backward(int W, int H, int gx, int gy, const Imag
                                         const float* campos, float* dL_dvalues, bool exact, hipStream_t stream);
 // distance mode, behind the per-Gaussian backward kernel: dL_dmean3D[g] += dL_dvalues[g] * (means3D[g] - campos) / |means3D[g] - campos| (0 at distance 0)
 hipError_t launch_depth_distance_fold(int P, const float* means3D, const float* campos, const float* dL_dvalues, float* dL_dmean3D, hipStream_t stream);
+// the contribution pass (contrib/contrib.hip: render_contrib_kernel): per Gaussian the largest forward blend weight, the number of blended
+// pairs and their fixed-point sum over each tile's first tile_last entries, COMBINED into the three arrays (any may be nullptr) with integer
+// atomics; pixel_mask (nullable): pixels whose entry is 0 take no part; only reads the frame
+hipError_t launch_render_contrib(int W, int H, int gx, int gy, const ImageState& img, const BinningState& b, const GeometryState& g,
+                                 const float* subpixel_offset, const float* pixel_mask, float* max_weight, unsigned long long* hits,
+                                 unsigned long long* weight_sum_q32, bool exact, hipStream_t stream);
 
 struct BwdParams {
     int P, D, M, W, H;

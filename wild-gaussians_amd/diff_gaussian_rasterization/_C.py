@@ -64,7 +64,7 @@ def binding_name() -> str:
 
 
 from ._abi import (_ALLOC_FN, _vp, _i, _f, _ShTone, _SecondImage, _RawGaussians, _RecolorParent, _CallOptions, _ForwardArgs,  # noqa: E402
-                    _BackwardArgs, _ProjectArgs, _DepthArgs, _DepthGrad)   # (pure ctypes)
+                    _BackwardArgs, _ProjectArgs, _DepthArgs, _DepthGrad, _ContribArgs)   # (pure ctypes)
 
 _lib.wg_rasterize_forward.restype = _i
 _lib.wg_rasterize_forward.argtypes = [_ALLOC_FN, _vp, _ALLOC_FN, _vp, _ALLOC_FN, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp,
@@ -84,6 +84,8 @@ _lib.wg_project_radii.restype = _i
 _lib.wg_project_radii.argtypes = [C.POINTER(_ProjectArgs)]
 _lib.wg_render_depth.restype = _i
 _lib.wg_render_depth.argtypes = [C.POINTER(_DepthArgs)]
+_lib.wg_render_contributions.restype = _i
+_lib.wg_render_contributions.argtypes = [C.POINTER(_ContribArgs)]
 for _name in ("wg_geometry_buffer_size", "wg_geometry_buffer_size_rows", "wg_binning_buffer_size"):
     getattr(_lib, _name).restype = C.c_size_t
     getattr(_lib, _name).argtypes = [_i]
@@ -943,6 +945,77 @@ def render_depth(geomBuffer, binningBuffer, imageBuffer, num_rendered, P, image_
 
 
 # ----------------------------------------------------------------------------------------------------------
+# The contribution pass (wg_render_contributions): per Gaussian the largest blend weight, the number of blended pairs and their fixed-point
+# sum over a finished frame, combined into caller-owned [P] arrays with integer atomics.
+CONTRIB_CAPACITY_MSG = ("contributions cannot be combined with binning_capacity: a fixed-capacity frame that did not fit has no lists to walk, "
+                        "and its verdict is not known when the contribution pass is queued")
+CONTRIB_NONE_MSG = "at least one of max_weight, hits and weight_sum_q32 must be given"
+CONTRIB_MASK_MSG = "contribution_mask must be a float32 tensor of H * W elements on the frame's HIP device"
+
+
+def _contrib_output_msg(name, dtype):
+    return f"{name} must be a contiguous {dtype} tensor of P elements on the frame's HIP device"
+
+
+def _check_contrib_arguments(geomBuffer, binningBuffer, imageBuffer, num_rendered, P, image_height, image_width, max_weight, hits, weight_sum_q32,
+                             pixel_mask, subpixel_offset):
+    """What render_contributions refuses: the outputs first (none at all; type, dtype, size, layout, device of each), then the frame's size, the
+    mask, the sub-pixel offsets and the buffers.  The compiled binding makes the same checks in the same order with the same messages
+    (csrc/torch_binding.cpp: RenderContributions)."""
+    device = imageBuffer.device
+    if max_weight is None and hits is None and weight_sum_q32 is None:
+        raise RuntimeError(CONTRIB_NONE_MSG)
+    for name, t, dtype, dname in (("max_weight", max_weight, torch.float32, "float32"), ("hits", hits, torch.int64, "int64"),
+                                  ("weight_sum_q32", weight_sum_q32, torch.int64, "int64")):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != int(P) or not t.is_contiguous()
+                              or t.device != device):
+            raise RuntimeError(_contrib_output_msg(name, dname))
+    if int(P) < 0 or int(num_rendered) < 0 or int(image_height) <= 0 or int(image_width) <= 0:
+        raise RuntimeError("P and num_rendered must not be negative, image_height and image_width must be positive")
+    N = int(image_height) * int(image_width)
+    if pixel_mask is not None and (not isinstance(pixel_mask, torch.Tensor) or pixel_mask.dtype != torch.float32 or pixel_mask.numel() != N
+                                   or pixel_mask.device != device):
+        raise RuntimeError(CONTRIB_MASK_MSG)
+    if subpixel_offset is not None and subpixel_offset.numel() != 0 and (
+            subpixel_offset.dtype != torch.float32 or subpixel_offset.numel() != 2 * N or subpixel_offset.device != device):
+        raise RuntimeError("subpixel_offset must be float32 with H * W * 2 elements on the frame's HIP device")
+    if not (geomBuffer.is_cuda and binningBuffer.is_cuda and imageBuffer.is_cuda):
+        raise RuntimeError("the frame's buffers must live on a HIP device")
+
+
+def render_contributions(geomBuffer, binningBuffer, imageBuffer, num_rendered, P, image_height, image_width, max_weight, hits, weight_sum_q32,
+                         pixel_mask=None, subpixel_offset=None, options=None, accumulate=True, debug=False):
+    """Combine what each Gaussian contributed to the finished frame these three buffers belong to (what rasterize_gaussians returned;
+    num_rendered = its first element) into max_weight (float32 [P]), hits (int64 [P]) and weight_sum_q32 (int64 [P]; the sum of
+    floor(w * 2^32)), any of which may be None (wg_render_contributions) -- one launch on torch's current stream that only reads the frame
+    and uses integer atomics, so two calls give the same bits.  pixel_mask: float32, H * W elements; a pixel whose entry is 0 takes no part.
+    accumulate=False zero-fills the given arrays under the same call first.  subpixel_offset / options: the frame's.  Returns None."""
+    opts = resolve_call_options(options)
+    H, W = int(image_height), int(image_width)
+    if _torch_ext is not None:
+        return _torch_ext.render_contributions(geomBuffer, binningBuffer, imageBuffer, int(num_rendered), int(P), H, W, max_weight, hits,
+                                               weight_sum_q32, pixel_mask, subpixel_offset, opts, bool(accumulate), bool(debug))
+    _check_contrib_arguments(geomBuffer, binningBuffer, imageBuffer, num_rendered, P, H, W, max_weight, hits, weight_sum_q32, pixel_mask,
+                             subpixel_offset)
+    if int(P) == 0:   # no Gaussian: nothing to fill, nothing to walk (an empty tensor has no address to hand to the library)
+        return None
+    device = imageBuffer.device
+    keep = [t.contiguous() if t is not None and t.numel() != 0 else None for t in (pixel_mask, subpixel_offset)]
+    a = _ContribArgs()
+    a.struct_size = C.sizeof(a)
+    a.P, a.R, a.width, a.height, a.debug = int(P), int(num_rendered), W, H, int(bool(debug))
+    a.geom_buffer, a.binning_buffer, a.image_buffer = geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr()
+    a.pixel_mask, a.subpixel_offset = (None if t is None else t.data_ptr() for t in keep)
+    ob = _CallOptions(*opts)
+    a.options = C.pointer(ob)
+    a.max_weight, a.hits, a.weight_sum_q32 = (None if t is None else t.data_ptr() for t in (max_weight, hits, weight_sum_q32))
+    a.accumulate, a.stream = int(bool(accumulate)), _stream(device)
+    with torch.cuda.device(device):
+        _check(_lib.wg_render_contributions(C.byref(a)), "wg_render_contributions")
+    return None
+
+
+# ----------------------------------------------------------------------------------------------------------
 # Introspection for the parity tests: typed views into the opaque scratch buffers (device tensors, no copy).
 def _from_ptr(ptr, shape, dtype, owner):
     # torch.frombuffer cannot wrap device memory; the CUDA array interface can
@@ -1029,7 +1102,7 @@ def version() -> str:
 
 # ----------------------------------------------------------------------------------------------------------
 # Per-stage HIP-event timing (wg_profile_* in wg_rasterizer.h); used by bench.py for the roofline object.
-STAGE_COUNT = 11  # WG_STAGE_COUNT (include/wg_rasterizer.h)
+STAGE_COUNT = 12  # WG_STAGE_COUNT (include/wg_rasterizer.h)
 
 
 class _StageTimes(C.Structure):

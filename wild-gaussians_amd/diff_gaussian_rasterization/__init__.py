@@ -23,6 +23,8 @@ import torch
 import torch.nn as nn
 
 from . import _C
+from . import contributions as _contrib
+from .contributions import ContributionStats, collect_contributions   # per-Gaussian contribution statistics (wg_render_contributions)
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians"]
 call_options = _C.call_options   # `with call_options(deterministic_backward=1): ...` (thread-local, scoped; see _C.py)
@@ -79,7 +81,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                 sh_mul=None, sh_offset=None, sh_pre_clamp_max=None, sh_post_clamp_max=None, binning_capacity=None, colors_precomp2=None,
                 filter_3D=None, sh_second=False, sh_mul2=None, sh_offset2=None, sh_pre_clamp_max2=None, sh_post_clamp_max2=None, call_options=None,
-                colour_gradients_only=None, grad_mode=True, depth_grad=False, return_depth=None):
+                colour_gradients_only=None, grad_mode=True, contributions=None, depth_grad=False, return_depth=None):
         rs = raster_settings
         native_args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                        rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.kernel_size, rs.subpixel_offset,
@@ -118,6 +120,13 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raise Exception(_C.DEPTH_CAPACITY_MSG)
         elif depth_grad:
             raise Exception("depth_grad=True is the gradient of the depth output: pass return_depth too")
+        # the contribution pass over the finished frame (wg_render_contributions): (stats, mask) or None; refused now, before anything is rendered
+        contrib_mask = None
+        if contributions is not None:
+            _contrib.check_stats(contributions[0], means3D.shape[0], means3D.device)
+            contrib_mask = _contrib.check_mask(contributions[1], rs.image_height, rs.image_width, means3D.device)
+            if binning_capacity is not None:
+                raise Exception(_C.CONTRIB_CAPACITY_MSG)
         if binning_capacity is not None:   # no host rendezvous (wg_forward_args::binning_capacity), capturable in a hipGraph
             extra["binning_capacity"] = int(binning_capacity)
         # a second set of precomputed colours composited in the same walk (wg_second_image)
@@ -174,6 +183,15 @@ class _RasterizeGaussians(torch.autograd.Function):
             else:
                 ctx.mark_non_differentiable(depth)
             out += (depth,)
+        if contributions is not None:
+            # and one more that combines what each Gaussian contributed to it into the caller's arrays; the frame is only read, the output
+            # tuple is what it was, nothing here takes a gradient
+            stats = contributions[0]
+            _call_native(lambda *a: _C.render_contributions(*a, options=ctx.call_options, accumulate=True, debug=rs.debug),
+                         (geom_buf, binning_buf, img_buf, num_rendered, means3D.shape[0], rs.image_height, rs.image_width, stats.max_weight,
+                          stats.hits, stats.weight_sum_q32, contrib_mask, rs.subpixel_offset), rs.debug, "snapshot_contrib.dump",
+                         "the contribution pass")
+            stats.views += 1
         return out
 
     @staticmethod
@@ -193,7 +211,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         extra = dict(options=ctx.call_options, colour_gradients_only=ctx.colour_only)   # the frame's forward call's
         if ctx.colour_only:   # dL_dcolors and nothing else: the geometry inputs' .grad stay as they were
             g_colors = _call_native(lambda *a: _C.rasterize_gaussians_backward(*a, **extra), native_args, rs.debug, "snapshot_bw.dump", "backward")[1]
-            return (None, None, None, g_colors) + (None,) * 22
+            return (None, None, None, g_colors) + (None,) * 23
         # dL_dcolors / dL_dcov3D are intermediates of a plain SH + scales/rotations call: wanted only where the input takes a gradient (what is not
         # wanted comes back as None, neither allocated nor stored)
         extra["want"] = (ctx.needs_input_grad[3], ctx.needs_input_grad[7])
@@ -222,22 +240,36 @@ class _RasterizeGaussians(torch.autograd.Function):
             g_mul, g_offset = shaped(res[8], ctx.sh_tone[0]), shaped(res[9], ctx.sh_tone[1])
         # the scalars' gradient, where return_depth was a tensor that takes one (its place among forward()'s inputs: the last)
         g_values = None
-        if grad_depth is not None and isinstance(ctx.depth_source, torch.Tensor) and ctx.needs_input_grad[25]:
+        if grad_depth is not None and isinstance(ctx.depth_source, torch.Tensor) and ctx.needs_input_grad[26]:
             g_values = res[-1].view(ctx.depth_source.shape)
         # order of forward()'s inputs; None for raster_settings, the clamp constants and the options
         return (g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3Ds, None, g_mul, g_offset, None, None, None, g_colors2, None,
-                None, g_mul2, g_offset2, None, None, None, None, None, None, g_values)
+                None, g_mul2, g_offset2, None, None, None, None, None, None, None, g_values)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                         sh_mul=None, sh_offset=None, sh_pre_clamp_max=None, sh_post_clamp_max=None, binning_capacity=None, colors_precomp2=None,
                         filter_3D=None, sh_second=False, sh_mul2=None, sh_offset2=None, sh_pre_clamp_max2=None, sh_post_clamp_max2=None, call_options=None,
-                        *, colour_gradients_only=None, return_depth=None, depth_grad=False):
+                        *, colour_gradients_only=None, return_depth=None, depth_grad=False, contributions=None, contribution_mask=None):
     _C._colour_mode(colour_gradients_only)   # (an unknown string: ValueError, before anything touches the device)
-    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                     raster_settings, sh_mul, sh_offset, sh_pre_clamp_max, sh_post_clamp_max, binning_capacity, colors_precomp2,
-                                     filter_3D, sh_second, sh_mul2, sh_offset2, sh_pre_clamp_max2, sh_post_clamp_max2, call_options,
-                                     colour_gradients_only, torch.is_grad_enabled(), bool(depth_grad), return_depth)
+    # contributions=: the keyword, else what an open `with collect_contributions(stats, mask)` block of this thread still holds -- its FIRST
+    # forward call takes it (handed back if that call raises)
+    taken = False
+    if contributions is None:
+        if contribution_mask is not None:
+            raise Exception("contribution_mask masks the contribution pass: pass contributions too")
+        contributions, contribution_mask = _contrib.take_pending()
+        taken = contributions is not None
+    try:
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                         raster_settings, sh_mul, sh_offset, sh_pre_clamp_max, sh_post_clamp_max, binning_capacity, colors_precomp2,
+                                         filter_3D, sh_second, sh_mul2, sh_offset2, sh_pre_clamp_max2, sh_post_clamp_max2, call_options,
+                                         colour_gradients_only, torch.is_grad_enabled(),
+                                         None if contributions is None else (contributions, contribution_mask), bool(depth_grad), return_depth)
+    except BaseException:
+        if taken:
+            _contrib.restore_pending(contributions, contribution_mask)
+        raise
 
 
 class GaussianRasterizer(nn.Module):
@@ -283,8 +315,20 @@ class GaussianRasterizer(nn.Module):
                 sh_offset2: Optional[torch.Tensor] = None, sh_pre_clamp_max2: Optional[float] = None,
                 sh_post_clamp_max2: Optional[float] = None, exact_compositing: Optional[bool] = None,
                 deterministic_backward: Optional[bool] = None, grad_record: Optional[bool] = None,
-                colour_gradients_only=None, return_depth=None, depth_grad: bool = False):
-        """`depth_grad=True` (keyword-only, beyond the reference; with `return_depth=`): `depth` is DIFFERENTIABLE -- with respect to the call's
+                colour_gradients_only=None, return_depth=None, depth_grad: bool = False, contributions=None, contribution_mask=None):
+        """`contributions=stats` (keyword-only, beyond the reference): a `ContributionStats(P, device)`.  After the frame is finished, one more
+        walk over its lists combines into `stats`, per Gaussian and over the (pixel, Gaussian) pairs this call blended, the largest blend
+        weight w = alpha * T (`max_weight`), the number of pairs (`hits`) and the sum of floor(w * 2^32) (`weight_sum_q32`), and
+        `stats.views` goes up by one (wg_render_contributions).  Integer atomics only: two sweeps give the same bits.  The published
+        pruning criteria are functions of these three (`stats.keep_mask(...)`; wg_integration.prune_by_contribution).
+        `contribution_mask=`: bool or float32, [H, W] or [1, H, W]; a pixel whose entry is 0 / False takes no part (the training mask, a
+        thresholded uncertainty).  The output tuple is unchanged and nothing takes a gradient.  Works under `torch.no_grad()`, with every
+        colour source, on a frame served by geometry reuse and beside `return_depth`; refused with `binning_capacity`; a wrong type, shape,
+        dtype or device raises before anything is rendered.  None = what an open `with collect_contributions(stats, mask):` block of the
+        calling thread holds, which feeds the FIRST forward call of the block only (a caller's render makes two or three calls over the same
+        geometry); no block: nothing new runs.
+
+        `depth_grad=True` (keyword-only, beyond the reference; with `return_depth=`): `depth` is DIFFERENTIABLE -- with respect to the call's
         geometry inputs (`means3D`, `means2D` as the carrier of the screen-space gradient, `opacities`, `scales` / `rotations` or `cov3D_precomp`;
         with `filter_3D=` the RAW parameters), to a `return_depth` tensor that requires grad, and in `"distance"` mode to `means3D` through
         v = |means3D - campos| as well (`campos` is a settings field and takes none).  A loss on depth then costs ONE more per-tile walk in the
@@ -370,4 +414,5 @@ class GaussianRasterizer(nn.Module):
             sh_second, sh_mul2, sh_offset2, sh_pre_clamp_max2, sh_post_clamp_max2,
             None if exact_compositing is None and deterministic_backward is None and grad_record is None else
             dict(exact_compositing=exact_compositing, deterministic_backward=deterministic_backward, grad_record=grad_record),
-            colour_gradients_only=colour_gradients_only, return_depth=return_depth, depth_grad=depth_grad)
+            colour_gradients_only=colour_gradients_only, return_depth=return_depth, depth_grad=depth_grad,
+            contributions=contributions, contribution_mask=contribution_mask)

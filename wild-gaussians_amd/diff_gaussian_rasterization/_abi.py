@@ -64,3 +64,10 @@ class _DepthArgs(C.Structure):  # wg_depth_args
     _fields_ = ([("struct_size", C.c_size_t)] + [(n, _i) for n in ("P", "R", "width", "height")] +
                 [(n, _vp) for n in ("geom_buffer", "binning_buffer", "image_buffer", "subpixel_offset", "values", "means3D", "campos")] +
                 [("options", C.POINTER(_CallOptions)), ("out_depth", _vp), ("debug", _i), ("stream", _vp)])
+
+
+class _ContribArgs(C.Structure):  # wg_contrib_args
+    _fields_ = ([("struct_size", C.c_size_t)] + [(n, _i) for n in ("P", "R", "width", "height")] +
+                [(n, _vp) for n in ("geom_buffer", "binning_buffer", "image_buffer", "subpixel_offset", "pixel_mask")] +
+                [("options", C.POINTER(_CallOptions))] + [(n, _vp) for n in ("max_weight", "hits", "weight_sum_q32")] +
+                [("accumulate", _i), ("debug", _i), ("stream", _vp)])

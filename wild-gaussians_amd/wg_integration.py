@@ -497,3 +497,53 @@ def fuse_evaluation_lpips(evaluation_module):
             evaluation_module._lpips = original
         fused.clear()
     return undo
+
+
+def contribution_sweep(trainer, cameras, masks=None):
+    """Per-Gaussian contribution statistics of `trainer`'s model over `cameras` -> `diff_gaussian_rasterization.ContributionStats`: for every
+    Gaussian the largest blend weight alpha * T any pixel of any of the views gave it, the number of pixels it was blended into and its
+    summed weight (what the published pruning criteria are functions of).  One `trainer.render(camera)` per camera under `torch.no_grad()`,
+    each inside `collect_contributions`, which feeds the FIRST rasterizer call of the render only (the caller's `_render_internal` makes two
+    or three over the same geometry).  `cameras`: anything with `len()` and integer indexing (the trainer's `train_cameras`).  `masks`: None,
+    or one bool / float32 [H, W] (or [1, H, W]) tensor or None per camera; pixels whose entry is 0 take no part (the training masks, a
+    thresholded uncertainty).  Integer atomics only: two sweeps give the same bits."""
+    from diff_gaussian_rasterization import ContributionStats, collect_contributions
+    model = trainer.model
+    xyz = model.xyz
+    n = len(cameras)
+    if masks is not None and len(masks) != n:
+        raise ValueError("masks must hold one entry (a tensor or None) per camera")
+    stats = ContributionStats(xyz.shape[0], xyz.device)
+    with torch.no_grad():
+        for k in range(n):
+            mask = None if masks is None else masks[k]
+            if mask is not None and not isinstance(mask, torch.Tensor):
+                mask = torch.as_tensor(mask)
+            if mask is not None:
+                mask = mask.to(xyz.device)
+            with collect_contributions(stats, mask):
+                trainer.render(cameras[k])
+    if stats.views != n:
+        raise RuntimeError(f"contribution_sweep: {n} cameras were rendered but {stats.views} frames were collected -- the render did not go "
+                           "through diff_gaussian_rasterization.GaussianRasterizer")
+    return stats
+
+
+def prune_by_contribution(trainer, cameras, *, masks=None, **thresholds) -> int:
+    """Remove the Gaussians of `trainer`'s model that fail `ContributionStats.keep_mask(**thresholds)` (min_max_weight=, min_hits=,
+    min_weight_sum=) over a `contribution_sweep` of `cameras` -> the number removed.  The removal is the model's own: `_prune_points(mask)`
+    (or `_prune(mask)` where the model names it so), which shrinks the parameters, the optimizer state and the densification statistics
+    together.  Floaters and the leftovers of transient objects -- Gaussians no training view blends with a weight worth keeping, or only in
+    masked pixels -- go this way before an export or a fine-tune.  Nothing calls it by default."""
+    if not thresholds:
+        raise ValueError("prune_by_contribution needs at least one threshold: min_max_weight=, min_hits= or min_weight_sum=")
+    model = trainer.model
+    prune = getattr(model, "_prune_points", None) or getattr(model, "_prune", None)
+    if prune is None:
+        raise AttributeError("the model has neither _prune_points nor _prune")
+    keep = contribution_sweep(trainer, cameras, masks=masks).keep_mask(**thresholds)
+    removed = int((~keep).sum())
+    if removed:
+        with torch.no_grad():
+            prune(~keep)
+    return removed
