@@ -242,8 +242,37 @@ typedef struct wg_backward_args {
 #define WG_COLOUR_GRADIENTS_ATOMIC 1
 #define WG_COLOUR_GRADIENTS_FIXED_ORDER 2
 
+/* The gradient of the distortion pass (wg_render_distortion, below) inside the frame's backward call: one more per-tile walk that adds into the
+ * gradient record before the per-Gaussian kernel runs -- behind the depth block's walk when both are present --, so that the geometry gradients come
+ * out as those of the image loss PLUS the distortion loss.  With g = dL_ddistortion[pixel] and the forward pass's moments (A, D', Q', c), u_i = v_i - c:
+ *   d dist / d w_i = m_i = Q' + u_i (A u_i - 2 D');  dL/dalpha_i = g T_i (m_i - R_i), R_i the reference's accum_rec recursion (backward.cu:555-561)
+ *   for the "channel" m, back to front, no background term; from dL/dalpha on the reference's chain (backward.cu:568-603).  The abs-gradient
+ *   (dL_dmean2D.z) receives |q_dist| beside |q_image|.  dL/dv_g = sum over g's pairs of 2 g w_i (A u_i - D'); the pivot takes no gradient.
+ *   moments: float[4*H*W], what wg_render_distortion wrote into out_moments for THIS frame with THESE values.
+ *   values: float[P], the scalars of the forward distortion pass; or NULL = the distance to the camera (reads the call's means3D and campos):
+ *     dL_dmean3D then also receives dL_dvalues[g] * (x_g - campos) / v_g (0 where v_g == 0).  campos takes no gradient.
+ *   dL_dvalues: float[P], required in both modes, overwritten in full, zero for Gaussians without instances.
+ * Needs the atomic gradient record: WG_ERR_INVALID_ARGUMENT, before any launch, with colour_gradients_only != 0, deterministic_backward = 1,
+ * grad_record = 0, a struct_size smaller than the struct, a NULL dL_ddistortion, moments or (P > 0) dL_dvalues, distance mode without means3D /
+ * campos.  R = 0 or P = 0 zero-fill dL_dvalues and launch no walk.  No scratch, no host wait: the call captures like the one without the block. */
+typedef struct wg_distortion_grad {
+    size_t struct_size;            /* the CALLER's sizeof(wg_distortion_grad): fields are only ever appended */
+    const float* dL_ddistortion;   /* [H*W] */
+    const float* moments;          /* [4*H*W]: the planes A, D', Q', c of the forward distortion pass */
+    const float* values;           /* [P] or NULL (distance) */
+    float* dL_dvalues;             /* [P], fully overwritten */
+} wg_distortion_grad;
+/* What a backward call may carry beyond wg_backward_args, whose size tests pin: blocks by pointer, fields only ever appended. */
+typedef struct wg_backward_extras {
+    size_t struct_size;                     /* the CALLER's sizeof(wg_backward_extras) */
+    const wg_distortion_grad* distortion;   /* the distortion pass's gradient in the same call, or NULL */
+} wg_backward_extras;
+
 int wg_rasterize_forward_ex(const wg_forward_args* args);
 int wg_rasterize_backward_ex(const wg_backward_args* args);
+/* wg_rasterize_backward_ex with the blocks of `extras`.  extras = NULL, or every block NULL: exactly wg_rasterize_backward_ex, no new code runs.
+ * WG_ERR_INVALID_ARGUMENT for an extras struct smaller than its first published size (16 bytes). */
+int wg_rasterize_backward_with(const wg_backward_args* args, const wg_backward_extras* extras);
 /* num_rendered and fits (1 / 0) of the forward call that produced image_buffer; synchronises the stream. */
 int wg_forward_status(char* image_buffer, int width, int height, int* num_rendered, int* fits, void* stream);
 
@@ -362,6 +391,36 @@ typedef struct wg_depth_args {
     void* stream;
 } wg_depth_args;
 int wg_render_depth(const wg_depth_args* args);
+
+/* ---- the distortion pass: the Mip-NeRF 360 / 2DGS distortion term of a FINISHED frame ----
+ *   out_distortion[pixel] = sum_{j < i} w_i w_j (v_i - v_j)^2,  w = alpha * T over the (pixel, Gaussian) pairs the frame's forward call blended
+ * (the depth pass's predicate, with the forward call's own decisions, alpha and T), computed as A Q' - D'^2 of the CENTRED moments
+ *   A = sum w,  D' = sum w u,  Q' = sum w u^2,  u_i = v_i - c (one float32 subtraction),  c = the v of the pixel's first blended instance:
+ * the term is invariant under a shift of v, and centred sums do not cancel where the uncentred A Q - D^2 of a three-channel (1, v, v^2) render does
+ * (thin surfaces far from the camera).  Not clamped: >= 0 in exact arithmetic, a last-bit negative value can come out.  A pixel without a
+ * contributor gives 0; no background term, no normalisation.
+ *   values / means3D / campos, geom_buffer / binning_buffer / image_buffer, R, subpixel_offset, options: as wg_render_depth takes them, with its
+ *     checks, its refusals, its WG_ERR_SPECULATION behaviour and its exact_compositing match.
+ *   out_distortion: float[H*W], required, fully overwritten.
+ *   out_moments: float[4*H*W] or NULL: the planes (A, D', Q', c), fully overwritten, what wg_distortion_grad reads in the frame's backward call.
+ * One launch on `stream` over each tile's list up to tile_last; the three buffers are only READ.  No scratch, no allocator, no atomics, no host
+ * wait (but for a deferred frame's verdict).  P = 0 or R = 0 zero-fill the outputs and return WG_OK.  Two calls give the same bits.
+ * Fields are only ever appended. */
+typedef struct wg_distortion_args {
+    size_t struct_size;   /* the CALLER's sizeof(wg_distortion_args) */
+    int P, R, width, height;
+    char *geom_buffer, *binning_buffer, *image_buffer;
+    const float* subpixel_offset;   /* the frame's float[H*W*2], or NULL */
+    const float* values;            /* [P] or NULL */
+    const float* means3D;           /* [P*3], read when values is NULL */
+    const float* campos;            /* [3], device, read when values is NULL */
+    const wg_call_options* options; /* NULL = WG_CALL_OPTIONS_DEFAULT */
+    float* out_distortion;          /* [H*W], fully overwritten */
+    float* out_moments;             /* [4*H*W] or NULL, fully overwritten */
+    int debug;                      /* 1: synchronise behind the launch and report (as the other calls' debug) */
+    void* stream;
+} wg_distortion_args;
+int wg_render_distortion(const wg_distortion_args* args);
 
 /* ---- the contribution pass: what each Gaussian contributed to a FINISHED frame ----
  * Over the (pixel, Gaussian) pairs the frame's forward call blended (the depth pass's predicate), with w = alpha * T the forward call's own

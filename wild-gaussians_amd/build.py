@@ -39,6 +39,10 @@ SOURCES = {
                                                  # render_fwd.hip's flags, so that the sum has the forward kernel's instruction and its bits
     "depth/depth_bwd.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],   # the depth pass's gradient (wg_depth_grad): render_bwd.hip's walk with one
                                                                             # channel, adding into the same gradient record; render_bwd.hip's flags
+    "distortion/distortion.hip": ["-fno-slp-vectorize"],   # the distortion pass (wg_render_distortion): depth.hip's walk with the blend weights' centred
+                                                     # moments per pixel; depth.hip's flags (render_fwd.hip's)
+    "distortion/distortion_bwd.hip": ["-munsafe-fp-atomics", "-fno-slp-vectorize"],   # its gradient (wg_distortion_grad): depth_bwd.hip's walk with a
+                                                                                # per-(pixel, instance) value; depth_bwd.hip's flags
     "contrib/contrib.hip": ["-fno-slp-vectorize"],   # the contribution pass (wg_render_contributions): the forward walk over a finished frame
                                                      # with per-Gaussian integer reductions; render_fwd.hip's flags, so that alpha * T and T
                                                      # come out of the forward kernel's instructions
@@ -82,7 +86,7 @@ SOURCES = {
                                        # 1 + p * (m - 1), switches it off for itself with a pragma, and every statistic's term is rounded to
                                        # float32 before it is widened into a float64 sum, which no contraction can cross
 }
-HEADERS = ["wg_common.h", "wg_alpha.h", "wg_sort.h", "wg_act.h", os.path.join(INCLUDE, "wg_rasterizer.h"), os.path.join(INCLUDE, "wg_knn.h"),
+HEADERS = ["wg_common.h", "wg_alpha.h", "wg_sort.h", "wg_act.h", os.path.join("distortion", "distortion.h"), os.path.join(INCLUDE, "wg_rasterizer.h"), os.path.join(INCLUDE, "wg_knn.h"),
            os.path.join(INCLUDE, "wg_ssim.h"), os.path.join(INCLUDE, "wg_activations.h"), os.path.join(INCLUDE, "wg_densify.h"), os.path.join(INCLUDE, "wg_adam.h"), os.path.join(INCLUDE, "wg_sh_eval.h"),
            os.path.join(INCLUDE, "wg_filter3d.h"), os.path.join(INCLUDE, "wg_densify_prune.h"), os.path.join(INCLUDE, "wg_msssim.h"),
            os.path.join(INCLUDE, "wg_appearance_mlp.h"), os.path.join(INCLUDE, "wg_appearance_colour.h"),

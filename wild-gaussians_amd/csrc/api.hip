@@ -1,6 +1,7 @@
 // C-ABI entry points (include/wg_rasterizer.h) -- the orchestration that Rasterizer::forward / ::backward /
 // ::markVisible do in the reference (rasterizer_impl.cu:141-153, 198-340, 344-443).
 #include "wg_common.h"
+#include "distortion/distortion.h"
 
 #include <dlfcn.h>
 #include <limits>
@@ -661,6 +662,9 @@ std::atomic<uint64_t> g_clean_frames{0}, g_clean_backwards{0};
 std::atomic<uint64_t> g_sh_skip_backwards{0};
 std::atomic<uint64_t> g_contribution_calls{0};     // wg_render_contributions calls that launched the walk (R > 0); read-only option "contribution_calls"
 std::atomic<uint64_t> g_depth_grad_backwards{0};   // backward calls that ran the depth cotangent's walk (wg_depth_grad); read-only option "depth_grad_calls"
+// walks wg_render_distortion launched / backward calls that ran the distortion cotangent's walk (wg_distortion_grad); read-only options
+// "distortion_calls" / "distortion_grad_calls"
+std::atomic<uint64_t> g_distortion_calls{0}, g_distortion_grad_backwards{0};
 std::mutex g_mode_mu;
 FrameMode g_modes[64];
 unsigned g_mode_head = 0;
@@ -712,7 +716,7 @@ int remembered_mode(const char* image_buffer) {
 
 static int forward_impl(const wg_forward_args& a);
 static int recolor_impl(const wg_forward_args& a);
-static int backward_impl(const wg_backward_args& a);
+static int backward_impl(const wg_backward_args& a, const wg_distortion_grad* tgrad = nullptr);
 static int backward_colour_impl(const wg_backward_args& a, const wg::Options& opt);
 
 int wg_rasterize_forward(wg_alloc_fn geometry_alloc, void* geometry_user, wg_alloc_fn binning_alloc, void* binning_user,
@@ -1161,7 +1165,18 @@ int wg_rasterize_backward_ex(const wg_backward_args* args) {
     return backward_impl(a);
 }
 
-static int backward_impl(const wg_backward_args& a) {
+int wg_rasterize_backward_with(const wg_backward_args* args, const wg_backward_extras* extras) {
+    if (extras == nullptr) return wg_rasterize_backward_ex(args);
+    if (extras->struct_size < sizeof(size_t) + sizeof(const wg_distortion_grad*)) return WG_ERR_INVALID_ARGUMENT;   // (the first published size)
+    if (extras->distortion == nullptr) return wg_rasterize_backward_ex(args);
+    if (args == nullptr || args->struct_size < BACKWARD_ARGS_V05 || args->struct_size > sizeof(wg_backward_args)) return WG_ERR_INVALID_ARGUMENT;
+    wg_backward_args a{};
+    std::memcpy(&a, args, args->struct_size);
+    a.struct_size = sizeof(a);
+    return backward_impl(a, extras->distortion);
+}
+
+static int backward_impl(const wg_backward_args& a, const wg_distortion_grad* tgrad) {
     // (the body below reads the arguments under the reference interface's names)
     const int P = a.P, D = a.D, M = a.M, R = a.R, width = a.width, height = a.height, debug = a.debug;
     const float scale_modifier = a.scale_modifier, tan_fovx = a.tan_fovx, tan_fovy = a.tan_fovy, kernel_size = a.kernel_size;
@@ -1192,6 +1207,13 @@ static int backward_impl(const wg_backward_args& a) {
         if (a.colour_gradients_only != 0 || opt.deterministic_backward != 0 || opt.grad_record == 0) return WG_ERR_INVALID_ARGUMENT;
         if (dgrad->dL_ddepth == nullptr || (P > 0 && dgrad->dL_dvalues == nullptr)) return WG_ERR_INVALID_ARGUMENT;
         if (P > 0 && dgrad->values == nullptr && (means3D == nullptr || campos == nullptr)) return WG_ERR_INVALID_ARGUMENT;   // distance mode's inputs
+    }
+    // the distortion pass's gradient (wg_distortion_grad): the same kind of walk, refused in the same places
+    if (tgrad != nullptr) {
+        if (tgrad->struct_size < sizeof(wg_distortion_grad)) return WG_ERR_INVALID_ARGUMENT;
+        if (a.colour_gradients_only != 0 || opt.deterministic_backward != 0 || opt.grad_record == 0) return WG_ERR_INVALID_ARGUMENT;
+        if (tgrad->dL_ddistortion == nullptr || tgrad->moments == nullptr || (P > 0 && tgrad->dL_dvalues == nullptr)) return WG_ERR_INVALID_ARGUMENT;
+        if (P > 0 && tgrad->values == nullptr && (means3D == nullptr || campos == nullptr)) return WG_ERR_INVALID_ARGUMENT;   // distance mode's inputs
     }
     if (a.colour_gradients_only != 0) return backward_colour_impl(a, opt);
     // two colour sets over one walk: the thirteen sums go to the gradient record (or, deterministic mode, to fourteen-float slots)
@@ -1329,6 +1351,21 @@ static int backward_impl(const wg_backward_args& a) {
                                                                                     opt.exact_compositing != 0, stream), "render_depth_backward");
         }
     }
+    // The distortion cotangent's walk, behind the depth block's: the same record, the same place on the stream.
+    if (tgrad != nullptr) {
+        {
+            StageScope scope_(WG_STAGE_RENDER_DEPTH_BACKWARD, stream);
+            hipError_t e = hipMemsetAsync(tgrad->dL_dvalues, 0, (size_t)P * sizeof(float), stream);
+            if (e != hipSuccess) return hip_fail(e, "distortion dL_dvalues memset");
+        }
+        if (R > 0) {
+            g_distortion_grad_backwards.fetch_add(1, std::memory_order_relaxed);
+            WG_STAGE(WG_STAGE_RENDER_DEPTH_BACKWARD, wg::launch_render_distortion_backward(width, height, gx, gy, img, bin, geom, subpixel_offset,
+                                                                                         tgrad->dL_ddistortion, tgrad->moments, tgrad->values, means3D, campos,
+                                                                                         tgrad->dL_dvalues, opt.exact_compositing != 0, stream),
+                     "render_distortion_backward");
+        }
+    }
 
     wg::BwdParams bp;
     bp.P = P; bp.D = D; bp.M = M; bp.W = width; bp.H = height;
@@ -1357,6 +1394,8 @@ static int backward_impl(const wg_backward_args& a) {
     // distance mode: v = |x - campos| depends on the mean itself -- its direct term goes on top of what the per-Gaussian kernel wrote
     if (dgrad != nullptr && dgrad->values == nullptr && R > 0)
         WG_STAGE(WG_STAGE_RENDER_DEPTH_BACKWARD, wg::launch_depth_distance_fold(P, means3D, campos, dgrad->dL_dvalues, dL_dmean3D, stream), "depth_distance_fold");
+    if (tgrad != nullptr && tgrad->values == nullptr && R > 0)
+        WG_STAGE(WG_STAGE_RENDER_DEPTH_BACKWARD, wg::launch_distortion_distance_fold(P, means3D, campos, tgrad->dL_dvalues, dL_dmean3D, stream), "distortion_distance_fold");
     {
         hipError_t e = det_guard.release();
         if (e != hipSuccess) return hip_fail(e, "deterministic backward scratch release");
@@ -1521,6 +1560,42 @@ int wg_render_depth(const wg_depth_args* args) {
     wg::ImageState img = wg::ImageState::fromChunk(image_buffer, (size_t)width * height, (size_t)gx * gy);
     WG_STAGE(WG_STAGE_RENDER_DEPTH, wg::launch_render_depth(width, height, gx, gy, img, bin, geom, a.subpixel_offset, a.values, a.means3D, a.campos,
                                                             a.out_depth, opt.exact_compositing != 0, stream), "render_depth");
+    return WG_OK;
+}
+
+// The distortion pass (distortion/distortion.hip: render_distortion_kernel): wg_render_depth's checks and flow with two outputs.
+int wg_render_distortion(const wg_distortion_args* args) {
+    if (!args || args->struct_size < sizeof(wg_distortion_args)) return WG_ERR_INVALID_ARGUMENT;
+    const wg_distortion_args& a = *args;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(a.stream);
+    const int P = a.P, R = a.R, width = a.width, height = a.height, debug = a.debug;
+    const wg::Options opt = call_options_snapshot(a.options);
+    if (a.image_buffer != nullptr && P > 0) {   // the frame was composited with the other arithmetic: its stored decisions are not this call's
+        const int fwd_mode = remembered_mode(a.image_buffer);
+        if (fwd_mode >= 0 && fwd_mode != (opt.exact_compositing ? 1 : 0)) return WG_ERR_INVALID_ARGUMENT;
+    }
+    if (P < 0 || R < 0 || width <= 0 || height <= 0 || !a.out_distortion) return WG_ERR_INVALID_ARGUMENT;
+    if (P > 0 && (!a.geom_buffer || !a.binning_buffer || !a.image_buffer)) return WG_ERR_INVALID_ARGUMENT;
+    if (P > 0 && !a.values && !(a.means3D && a.campos)) return WG_ERR_INVALID_ARGUMENT;   // no scalar source
+    if (a.image_buffer != nullptr) {   // a deferred forward call's verdict, as in the backward passes
+        const int verdict = check_ticket(image_key(a.image_buffer), stream);
+        if (verdict != WG_OK) return verdict;
+    }
+    if (P == 0 || R == 0) {   // no lists to walk: every pixel is without a contributor
+        StageScope scope_(WG_STAGE_RENDER_DEPTH, stream);
+        hipError_t e = hipMemsetAsync(a.out_distortion, 0, (size_t)width * height * sizeof(float), stream);
+        if (e == hipSuccess && a.out_moments) e = hipMemsetAsync(a.out_moments, 0, 4 * (size_t)width * height * sizeof(float), stream);
+        if (e != hipSuccess) return hip_fail(e, "distortion memset");
+        return WG_OK;
+    }
+    const int gx = (width + wg::TILE_X - 1) / wg::TILE_X, gy = (height + wg::TILE_Y - 1) / wg::TILE_Y;
+    char *geom_buffer = a.geom_buffer, *binning_buffer = a.binning_buffer, *image_buffer = a.image_buffer;   // (fromChunk advances its argument)
+    wg::GeometryState geom = wg::GeometryState::fromChunk(geom_buffer, (size_t)P, false);
+    wg::BinningState bin = wg::BinningState::fromChunk(binning_buffer, (size_t)R, false);  // only point_list is used
+    wg::ImageState img = wg::ImageState::fromChunk(image_buffer, (size_t)width * height, (size_t)gx * gy);
+    g_distortion_calls.fetch_add(1, std::memory_order_relaxed);
+    WG_STAGE(WG_STAGE_RENDER_DEPTH, wg::launch_render_distortion(width, height, gx, gy, img, bin, geom, a.subpixel_offset, a.values, a.means3D, a.campos,
+                                                                 a.out_distortion, a.out_moments, opt.exact_compositing != 0, stream), "render_distortion");
     return WG_OK;
 }
 
@@ -1712,6 +1787,8 @@ int wg_get_option(const char* name) {
     // ... backward calls whose per-tile launch zeroed dL_dsh and whose per-Gaussian kernel stored the touched rows only
     if (std::strcmp(name, "sh_grad_skip_calls") == 0) return (int)std::min<uint64_t>(g_sh_skip_backwards.load(std::memory_order_relaxed), 0x7fffffffu);
     if (std::strcmp(name, "depth_grad_calls") == 0) return (int)std::min<uint64_t>(g_depth_grad_backwards.load(std::memory_order_relaxed), 0x7fffffffu);
+    if (std::strcmp(name, "distortion_calls") == 0) return (int)std::min<uint64_t>(g_distortion_calls.load(std::memory_order_relaxed), 0x7fffffffu);
+    if (std::strcmp(name, "distortion_grad_calls") == 0) return (int)std::min<uint64_t>(g_distortion_grad_backwards.load(std::memory_order_relaxed), 0x7fffffffu);
     if (std::strcmp(name, "contribution_calls") == 0) return (int)std::min<uint64_t>(g_contribution_calls.load(std::memory_order_relaxed), 0x7fffffffu);
     const OptionRow* r = find_option(name);
     return r ? r->get(options_snapshot()) : -1;

@@ -202,14 +202,15 @@ ForwardResult forward(const Scene& s, const torch::Tensor& opacity, const int H,
 
 // The reference's eight (rasterize_points.cu:201) and what the optional blocks add (undefined = not asked for).
 struct Gradients {
-    torch::Tensor means2D, colors, opacity, means3D, cov3D, sh, scales, rotations, colors2, mul, offset, mul2, offset2, values;   // values: with `depth` only
+    torch::Tensor means2D, colors, opacity, means3D, cov3D, sh, scales, rotations, colors2, mul, offset, mul2, offset2, values, values_t;   // values: with `depth` only; values_t: with `distortion` only
     std::vector<torch::Tensor> eight() const { return {means2D, colors, opacity, means3D, cov3D, sh, scales, rotations}; }
 };
 
 Gradients backward(const Scene& s, const torch::Tensor& radii, const torch::Tensor& dL_dout_color, const torch::Tensor& geomBuffer, const int R,
                    const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const py::object& sh_tone, const OptTensor& dL_dout_color2,
                    const py::object& raw_in, const py::object& sh_second, const wg_call_options& co, const int colour_only = 0,   // (wg_backward_args::colour_gradients_only)
-                   const bool want_colors = true, const bool want_cov3D = true, const py::object& depth = py::none()) {   // depth: wg_depth_grad
+                   const bool want_colors = true, const bool want_cov3D = true, const py::object& depth = py::none(),   // depth: wg_depth_grad
+                   const py::object& distortion = py::none()) {   // distortion: wg_distortion_grad (through wg_backward_extras)
     const auto dev = s.means3D.device();
     const c10::DeviceGuard guard(dev);
     const int P = static_cast<int>(s.means3D.size(0));
@@ -260,6 +261,39 @@ Gradients backward(const Scene& s, const torch::Tensor& radii, const torch::Tens
         }
         dLd = dLd.contiguous();
     }
+    // distortion = None | (dL_ddistortion [H, W], moments [4, H, W], source): the checks of _C.py's _check_distortion_grad_arguments, in its order,
+    // with its messages (an unknown string is a ValueError there and here)
+    torch::Tensor dLt, mom, tvalues;
+    bool dist_distance = false;
+    if (!distortion.is_none()) {
+        const char* source_msg = "return_distortion must be \"distance\" or a float32 [P] tensor of per-Gaussian scalars on the frame's HIP device";
+        const char* block_msg = "distortion is (dL_ddistortion, moments, source): the distortion cotangent [H, W], the forward pass's moments [4, H, W] "
+                                "and the frame's return_distortion source";
+        const char* cot_msg = "dL_ddistortion must be a float32 tensor of H * W elements on the frame's HIP device";
+        const char* mom_msg = "moments must be a float32 tensor of 4 * H * W elements on the frame's HIP device";
+        if (!(py::isinstance<py::tuple>(distortion) || py::isinstance<py::list>(distortion)) || py::len(distortion) != 3) throw std::runtime_error(block_msg);
+        const py::sequence sq = distortion.cast<py::sequence>();
+        const py::object cot = sq[0], mo = sq[1], source = sq[2];
+        if (!THPVariable_Check(cot.ptr())) throw std::runtime_error(cot_msg);
+        dLt = cot.cast<torch::Tensor>();
+        if (dLt.scalar_type() != torch::kFloat32 || dLt.numel() * 3 != dL_dout_color.numel() || dLt.device() != dL_dout_color.device()) throw std::runtime_error(cot_msg);
+        if (!THPVariable_Check(mo.ptr())) throw std::runtime_error(mom_msg);
+        mom = mo.cast<torch::Tensor>();
+        if (mom.scalar_type() != torch::kFloat32 || mom.numel() * 3 != 4 * dL_dout_color.numel() || mom.device() != dL_dout_color.device()) throw std::runtime_error(mom_msg);
+        dist_distance = py::isinstance<py::str>(source);
+        if (dist_distance) {
+            if (source.cast<std::string>() != "distance") throw py::value_error(source_msg);
+        } else {
+            if (!THPVariable_Check(source.ptr())) throw std::runtime_error(source_msg);
+            tvalues = source.cast<torch::Tensor>();
+            if (tvalues.scalar_type() != torch::kFloat32) throw std::runtime_error(source_msg);
+            if (tvalues.numel() != P64) throw std::runtime_error("distortion values must have P elements");
+            if (!tvalues.is_cuda() || tvalues.device() != dL_dout_color.device()) throw std::runtime_error(source_msg);
+            tvalues = tvalues.contiguous();
+        }
+        dLt = dLt.contiguous();
+        mom = mom.contiguous();
+    }
 
     const int H = static_cast<int>(dL_dout_color.size(1)), W = static_cast<int>(dL_dout_color.size(2));
     const Inputs in(s, dev);
@@ -307,6 +341,7 @@ Gradients backward(const Scene& s, const torch::Tensor& radii, const torch::Tens
     if (tone2.t.mul) g.mul2 = alloc({P, 3}, true);
     if (tone2.t.offset) g.offset2 = alloc({P, 3}, true);
     if (!depth.is_none()) g.values = alloc({P}, true);   // (the library fills it)
+    if (!distortion.is_none()) g.values_t = alloc({P}, true);   // (likewise)
     if (P == 0) return g;
 
     tone.t.dL_dmul = const_cast<float*>(ptr(g.mul)); tone.t.dL_doffset = const_cast<float*>(ptr(g.offset));
@@ -339,10 +374,19 @@ Gradients backward(const Scene& s, const torch::Tensor& radii, const torch::Tens
         dgrad.dL_ddepth = dLd.data_ptr<float>(); dgrad.values = depth_distance ? nullptr : dvalues.data_ptr<float>(); dgrad.dL_dvalues = g.values.data_ptr<float>();
         a.depth = &dgrad;
     }
+    wg_distortion_grad tgrad{};
+    wg_backward_extras extras{};
+    if (!distortion.is_none()) {   // wg_backward_args' size is pinned: the block travels in wg_backward_extras
+        tgrad.struct_size = sizeof(tgrad);
+        tgrad.dL_ddistortion = dLt.data_ptr<float>(); tgrad.moments = mom.data_ptr<float>();
+        tgrad.values = dist_distance ? nullptr : tvalues.data_ptr<float>(); tgrad.dL_dvalues = g.values_t.data_ptr<float>();
+        extras.struct_size = sizeof(extras);
+        extras.distortion = &tgrad;
+    }
     int status;
     {
         py::gil_scoped_release nogil;   // (as the forward call: a deferred frame's verdict may be waited for here)
-        status = wg_rasterize_backward_ex(&a);
+        status = distortion.is_none() ? wg_rasterize_backward_ex(&a) : wg_rasterize_backward_with(&a, &extras);
     }
     check(status, "wg_rasterize_backward");
     return g;
@@ -596,9 +640,69 @@ py::tuple RasterizeGaussiansExNoHint(const torch::Tensor& background, const torc
                                 colors2, filter_3D, sh_second, options, false);
 }
 
+// The distortion pass (wg_render_distortion): the distortion term of the finished frame these three buffers belong to -> distortion [H, W], or
+// with moments = true (distortion, moments [4, H, W]).  The checks of _C.py's _check_distortion_arguments, in its order, with its messages.
+py::object RenderDistortion(const torch::Tensor& geomBuffer, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const int R, const int P,
+                            const int image_height, const int image_width, const py::object& source, const OptTensor& means3D, const OptTensor& campos,
+                            const OptTensor& subpixel_offset, const std::tuple<int, int, int>& options, const bool want_moments, const bool debug) {
+    const char* source_msg = "return_distortion must be \"distance\" or a float32 [P] tensor of per-Gaussian scalars on the frame's HIP device";
+    const auto dev = imageBuffer.device();
+    const bool distance = py::isinstance<py::str>(source);
+    torch::Tensor values;
+    if (distance) {
+        if (source.cast<std::string>() != "distance") throw py::value_error(source_msg);
+    } else {
+        if (!THPVariable_Check(source.ptr())) throw std::runtime_error(source_msg);
+        values = source.cast<torch::Tensor>();
+        if (values.scalar_type() != torch::kFloat32) throw std::runtime_error(source_msg);
+        if (values.numel() != P) throw std::runtime_error("distortion values must have P elements");
+        if (!values.is_cuda() || values.device() != dev) throw std::runtime_error(source_msg);
+    }
+    if (distance) {
+        if (!means3D.has_value() || !campos.has_value()) throw std::runtime_error("distortion source \"distance\" needs means3D and campos");
+        if (means3D->scalar_type() != torch::kFloat32 || means3D->numel() != 3 * (int64_t)P || campos->scalar_type() != torch::kFloat32 || campos->numel() != 3)
+            throw std::runtime_error("means3D must be float32 with 3 * P elements, campos float32 with 3");
+        if (!means3D->is_cuda() || means3D->device() != dev || !campos->is_cuda() || campos->device() != dev)
+            throw std::runtime_error("means3D and campos must live on the frame's HIP device");
+    }
+    if (P < 0 || R < 0 || image_height <= 0 || image_width <= 0)
+        throw std::runtime_error("P and num_rendered must not be negative, image_height and image_width must be positive");
+    const int64_t N = (int64_t)image_height * image_width;
+    if (subpixel_offset.has_value() && subpixel_offset->numel() != 0 &&
+        (subpixel_offset->scalar_type() != torch::kFloat32 || subpixel_offset->numel() != 2 * N || subpixel_offset->device() != dev))
+        throw std::runtime_error("subpixel_offset must be float32 with H * W * 2 elements on the frame's HIP device");
+    if (!(geomBuffer.is_cuda() && binningBuffer.is_cuda() && imageBuffer.is_cuda())) throw std::runtime_error("the frame's buffers must live on a HIP device");
+
+    const c10::DeviceGuard guard(dev);
+    const auto f = imageBuffer.options().dtype(torch::kFloat32);
+    torch::Tensor dist = torch::empty({image_height, image_width}, f), mom;   // both fully written by the library
+    if (want_moments) mom = torch::empty({4, image_height, image_width}, f);
+    const auto m3 = distance ? means3D->contiguous() : torch::Tensor(), cam = distance ? campos->contiguous() : torch::Tensor(),
+               val = distance ? torch::Tensor() : values.contiguous(),
+               so = subpixel_offset.has_value() ? subpixel_offset->contiguous() : torch::Tensor();
+    const wg_call_options co = call_options(options);
+    wg_distortion_args a{};
+    a.struct_size = sizeof(a);
+    a.P = P; a.R = R; a.width = image_width; a.height = image_height; a.debug = debug;
+    if (P != 0) { a.geom_buffer = bytes_of(geomBuffer); a.binning_buffer = bytes_of(binningBuffer); a.image_buffer = bytes_of(imageBuffer); }
+    a.subpixel_offset = ptr(so); a.values = ptr(val); a.means3D = ptr(m3); a.campos = ptr(cam);
+    a.options = &co;
+    a.out_distortion = dist.data_ptr<float>();
+    a.out_moments = want_moments ? mom.data_ptr<float>() : nullptr;
+    a.stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream();
+    int status;
+    {
+        py::gil_scoped_release nogil;
+        status = wg_render_distortion(&a);
+    }
+    check(status, "wg_render_distortion");
+    if (want_moments) return py::make_tuple(dist, mom);
+    return py::cast(dist);
+}
+
 // -> the reference's eight, + (mul, offset, mul2, offset2) with sh_second, + dL_dcolors2 with a second colour set, + (mul, offset) with sh_tone,
-//    + dL_dvalues [P] last with the depth block (depth = None: absent)
-py::tuple RasterizeGaussiansBackwardDepth(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& colors,
+//    + the distortion's dL_dvalues [P] with the distortion block, + dL_dvalues [P] last with the depth block (None: absent)
+py::tuple RasterizeGaussiansBackwardDistortion(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& colors,
                                        const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier,
                                        const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix,
                                        const float tan_fovx, const float tan_fovy, const float kernel_size, const OptTensor& subpixel_offset,
@@ -606,11 +710,11 @@ py::tuple RasterizeGaussiansBackwardDepth(const torch::Tensor& background, const
                                        const torch::Tensor& geomBuffer, const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
                                        const bool debug, const py::object& sh_tone, const OptTensor& dL_dout_color2, const py::object& raw_in,
                                        const py::object& sh_second, const std::tuple<int, int, int>& options, const bool want_colors,
-                                       const bool want_cov3D, const py::object& depth) {
+                                       const bool want_cov3D, const py::object& depth, const py::object& distortion) {
     const Scene s{background, means3D, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, kernel_size,
                   opt(subpixel_offset), sh, degree, campos, debug};
     const Gradients g = backward(s, radii, dL_dout_color, geomBuffer, R, binningBuffer, imageBuffer, sh_tone, dL_dout_color2, raw_in, sh_second,
-                                 call_options(options), 0, want_colors, want_cov3D, depth);
+                                 call_options(options), 0, want_colors, want_cov3D, depth, distortion);
     py::list out;
     for (const auto& t : g.eight()) out.append(or_none(t));   // (None: dL_dcolors / dL_dcov3D that the caller did not want)
     if (!sh_second.is_none()) {
@@ -620,8 +724,25 @@ py::tuple RasterizeGaussiansBackwardDepth(const torch::Tensor& background, const
     } else if (!sh_tone.is_none()) {
         out.append(or_none(g.mul)); out.append(or_none(g.offset));
     }
-    if (!depth.is_none()) out.append(g.values);   // + dL_dvalues [P], last
+    if (!distortion.is_none()) out.append(g.values_t);   // + the distortion's dL_dvalues [P], in front of depth's
+    if (!depth.is_none()) out.append(g.values);          // + dL_dvalues [P], last
     return py::tuple(out);
+}
+
+// (without the distortion block)
+py::tuple RasterizeGaussiansBackwardDepth(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& colors,
+                                       const torch::Tensor& scales, const torch::Tensor& rotations, const float scale_modifier,
+                                       const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix,
+                                       const float tan_fovx, const float tan_fovy, const float kernel_size, const OptTensor& subpixel_offset,
+                                       const torch::Tensor& dL_dout_color, const torch::Tensor& sh, const int degree, const torch::Tensor& campos,
+                                       const torch::Tensor& geomBuffer, const int R, const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
+                                       const bool debug, const py::object& sh_tone, const OptTensor& dL_dout_color2, const py::object& raw_in,
+                                       const py::object& sh_second, const std::tuple<int, int, int>& options, const bool want_colors,
+                                       const bool want_cov3D, const py::object& depth) {
+    return RasterizeGaussiansBackwardDistortion(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
+                                                tan_fovx, tan_fovy, kernel_size, subpixel_offset, dL_dout_color, sh, degree, campos, geomBuffer, R,
+                                                binningBuffer, imageBuffer, debug, sh_tone, dL_dout_color2, raw_in, sh_second, options, want_colors,
+                                                want_cov3D, depth, py::none());
 }
 
 // (without the depth block: today's call)
@@ -676,6 +797,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {   // ext.cpp:15-19
     m.def("mark_visible", &markVisible);
     m.def("project_radii", &ProjectRadii);                                     // wg_project_radii: a frame's radii before it is rendered
     m.def("render_depth", &RenderDepth);                                       // wg_render_depth: a scalar per Gaussian composited over a finished frame
+    m.def("render_distortion", &RenderDistortion);                             // wg_render_distortion: the distortion term of a finished frame (+ its moments)
     m.def("render_contributions", &RenderContributions);                       // wg_render_contributions: per-Gaussian contribution statistics of a finished frame
     m.def("rasterize_gaussians_ex", &RasterizeGaussiansEx);                    // + the blocks of wg_forward_args, + the forward_only hint
     m.def("rasterize_gaussians_ex", &RasterizeGaussiansExNoHint);              //   (overload without the hint)
@@ -683,4 +805,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {   // ext.cpp:15-19
     m.def("rasterize_gaussians_backward_ex", &RasterizeGaussiansBackwardExAll);   //   (overload without the two flags: all eight)
     m.def("rasterize_gaussians_backward_colour", &RasterizeGaussiansBackwardColour);   // wg_backward_args::colour_gradients_only
     m.def("rasterize_gaussians_backward_depth", &RasterizeGaussiansBackwardDepth);     // + wg_backward_args::depth: (dL_ddepth, source) -> ..., dL_dvalues
+    m.def("rasterize_gaussians_backward_distortion", &RasterizeGaussiansBackwardDistortion);   // + wg_backward_extras::distortion: (dL_ddistortion, moments, source)
 }

@@ -64,7 +64,8 @@ def binding_name() -> str:
 
 
 from ._abi import (_ALLOC_FN, _vp, _i, _f, _ShTone, _SecondImage, _RawGaussians, _RecolorParent, _CallOptions, _ForwardArgs,  # noqa: E402
-                    _BackwardArgs, _ProjectArgs, _DepthArgs, _DepthGrad, _ContribArgs)   # (pure ctypes)
+                    _BackwardArgs, _ProjectArgs, _DepthArgs, _DepthGrad, _ContribArgs, _DistortionArgs, _DistortionGrad,
+                    _BackwardExtras)   # (pure ctypes)
 
 _lib.wg_rasterize_forward.restype = _i
 _lib.wg_rasterize_forward.argtypes = [_ALLOC_FN, _vp, _ALLOC_FN, _vp, _ALLOC_FN, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp,
@@ -86,6 +87,10 @@ _lib.wg_render_depth.restype = _i
 _lib.wg_render_depth.argtypes = [C.POINTER(_DepthArgs)]
 _lib.wg_render_contributions.restype = _i
 _lib.wg_render_contributions.argtypes = [C.POINTER(_ContribArgs)]
+_lib.wg_render_distortion.restype = _i
+_lib.wg_render_distortion.argtypes = [C.POINTER(_DistortionArgs)]
+_lib.wg_rasterize_backward_with.restype = _i
+_lib.wg_rasterize_backward_with.argtypes = [C.POINTER(_BackwardArgs), C.POINTER(_BackwardExtras)]
 for _name in ("wg_geometry_buffer_size", "wg_geometry_buffer_size_rows", "wg_binning_buffer_size"):
     getattr(_lib, _name).restype = C.c_size_t
     getattr(_lib, _name).argtypes = [_i]
@@ -498,6 +503,54 @@ def _check_depth_grad_arguments(depth, P, dL_dout_color):
         raise RuntimeError(DEPTH_SOURCE_MSG)
 
 
+# The distortion pass's gradient (wg_distortion_grad): the same kind of walk into the same record, refused in the same places with one message.
+DISTORTION_GRAD_MSG = ("distortion_grad adds the distortion loss's gradient into the frame's gradient record: it cannot be combined with "
+                       "colour_gradients_only, deterministic_backward = 1, grad_record = 0 or binning_capacity")
+DISTORTION_GRAD_BLOCK_MSG = ("distortion is (dL_ddistortion, moments, source): the distortion cotangent [H, W], the forward pass's moments [4, H, W] "
+                             "and the frame's return_distortion source")
+DISTORTION_GRAD_COTANGENT_MSG = "dL_ddistortion must be a float32 tensor of H * W elements on the frame's HIP device"
+DISTORTION_GRAD_MOMENTS_MSG = "moments must be a float32 tensor of 4 * H * W elements on the frame's HIP device"
+DISTORTION_SOURCE_MSG = 'return_distortion must be "distance" or a float32 [P] tensor of per-Gaussian scalars on the frame\'s HIP device'
+DISTORTION_CAPACITY_MSG = ("return_distortion cannot be combined with binning_capacity: a fixed-capacity frame that did not fit has no lists to walk, "
+                           "and its verdict is not known when the distortion pass is queued")
+
+
+def distortion_grad_refused(colour_only, opts, fixed_capacity=False) -> bool:
+    """What a distortion gradient cannot be combined with: what a depth gradient cannot (depth_grad_refused)."""
+    return depth_grad_refused(colour_only, opts, fixed_capacity)
+
+
+def check_distortion_source(source, P=None):
+    """What `return_distortion` / `source` may be, as far as no device is needed (P = None: the size is checked later).  An unknown string is a
+    ValueError, like colour_gradients_only's.  The compiled binding makes the same checks in the same order with the same messages."""
+    if isinstance(source, str):
+        if source != "distance":
+            raise ValueError(DISTORTION_SOURCE_MSG)
+        return
+    if not isinstance(source, torch.Tensor) or source.dtype != torch.float32:
+        raise RuntimeError(DISTORTION_SOURCE_MSG)
+    if P is not None and source.numel() != P:
+        raise RuntimeError("distortion values must have P elements")
+
+
+def _check_distortion_grad_arguments(distortion, P, dL_dout_color):
+    """What rasterize_gaussians_backward refuses of its `distortion` block, after the mode check in front of both bindings.  The compiled binding
+    makes the same checks in the same order with the same messages (csrc/torch_binding.cpp: DistortionBlock)."""
+    if not isinstance(distortion, (tuple, list)) or len(distortion) != 3:
+        raise RuntimeError(DISTORTION_GRAD_BLOCK_MSG)
+    dL_ddist, moments, source = distortion
+    device = dL_dout_color.device
+    if (not isinstance(dL_ddist, torch.Tensor) or dL_ddist.dtype != torch.float32 or dL_ddist.numel() * 3 != dL_dout_color.numel()
+            or dL_ddist.device != device):
+        raise RuntimeError(DISTORTION_GRAD_COTANGENT_MSG)
+    if (not isinstance(moments, torch.Tensor) or moments.dtype != torch.float32 or moments.numel() * 3 != 4 * dL_dout_color.numel()
+            or moments.device != device):
+        raise RuntimeError(DISTORTION_GRAD_MOMENTS_MSG)
+    check_distortion_source(source, P)
+    if isinstance(source, torch.Tensor) and (not source.is_cuda or source.device != device):
+        raise RuntimeError(DISTORTION_SOURCE_MSG)
+
+
 def _fill(a, device, P, degree, M, H, W, debug, scale_modifier, tan_fovx, tan_fovy, kernel_size, **tensors):
     """The fields wg_forward_args and wg_backward_args share; every other pointer field by name (None or zero-sized = NULL)."""
     a.struct_size = C.sizeof(a)
@@ -630,8 +683,13 @@ def _forward_ctypes(background, means3D, colors, opacity, scales, rotations, sca
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, kernel_size, subpixel_offset, dL_dout_color, sh,
                                  degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, sh_tone=None, dL_dout_color2=None, raw=None,
-                                 sh_second=None, options=None, colour_gradients_only=None, want=None, depth=None):
+                                 sh_second=None, options=None, colour_gradients_only=None, want=None, depth=None, distortion=None):
     """The reference's `rasterize_gaussians_backward` (rasterize_points.h:42-66) -> the eight tensors, plus by keyword:
+    distortion = (dL_ddistortion [H, W], moments [4, H, W], source): the cotangent of the frame's distortion output (render_distortion), the
+      moments that call returned and its source -- "distance" or the float32 [P] tensor of scalars.  One more per-tile walk adds the distortion
+      loss's gradient into the gradient record (wg_distortion_grad through wg_rasterize_backward_with), behind the depth block's when both are
+      given.  The result carries one more tensor, dL_dvalues [P] of the distortion's scalars: last, or IN FRONT of depth's dL_dvalues when
+      `depth` is given too (which stays last).  Refused where `depth` is.  None: today's call, nothing new runs.
     depth = (dL_ddepth [H, W], source): the cotangent of the frame's depth output (render_depth) and its source -- "distance" or the float32 [P]
       tensor of scalars.  One more per-tile walk adds the depth loss's gradient into the gradient record (wg_depth_grad), so the geometry
       gradients returned are those of the image loss plus the depth loss; in distance mode dL_dmeans3D also carries the direct term.  The result
@@ -663,6 +721,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             states.pop(ident, None)
     if depth is not None and depth_grad_refused(colour_only, opts):   # the mode checks, in front of both bindings
         raise RuntimeError(DEPTH_GRAD_MSG)
+    if distortion is not None and distortion_grad_refused(colour_only, opts):
+        raise RuntimeError(DISTORTION_GRAD_MSG)
     if colour_only and colour_only_refused(sh.numel() != 0, sh_tone is not None, dL_dout_color2 is not None, raw is not None,
                                            sh_second is not None, opts):
         raise RuntimeError(COLOUR_ONLY_MSG)
@@ -683,6 +743,12 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         _check_backward_arguments(means3D, radii, colors, scales, rotations, cov3D_precomp, sh, dL_dout_color, None, None, None, None)
         return _backward_colour_ctypes(background, means3D, colors, subpixel_offset, dL_dout_color, geomBuffer, R, binningBuffer, imageBuffer, debug, opts,
                                        _COLOUR_MODE_ABI[colour_only])
+    if _torch_ext is not None and distortion is not None:
+        return _torch_ext.rasterize_gaussians_backward_distortion(background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
+                                                                  viewmatrix, projmatrix, float(tan_fovx), float(tan_fovy), float(kernel_size),
+                                                                  subpixel_offset, dL_dout_color, sh, int(degree), campos, geomBuffer, int(R), binningBuffer,
+                                                                  imageBuffer, bool(debug), sh_tone, dL_dout_color2, raw, sh_second, opts, want_colors,
+                                                                  want_cov3D, depth, distortion)
     if _torch_ext is not None and depth is not None:
         return _torch_ext.rasterize_gaussians_backward_depth(background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
                                                              viewmatrix, projmatrix, float(tan_fovx), float(tan_fovy), float(kernel_size), subpixel_offset,
@@ -696,15 +762,18 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     _check_backward_arguments(means3D, radii, colors, scales, rotations, cov3D_precomp, sh, dL_dout_color, sh_tone, dL_dout_color2, raw, sh_second)
     if depth is not None:
         _check_depth_grad_arguments(depth, means3D.size(0), dL_dout_color)
+    if distortion is not None:
+        _check_distortion_grad_arguments(distortion, means3D.size(0), dL_dout_color)
     return _backward_ctypes(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
                             tan_fovy, kernel_size, subpixel_offset, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug,
-                            sh_tone, dL_dout_color2, raw, sh_second, opts, want_colors, want_cov3D, depth)
+                            sh_tone, dL_dout_color2, raw, sh_second, opts, want_colors, want_cov3D, depth, distortion)
 
 
 def _backward_ctypes(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                      kernel_size, subpixel_offset, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, sh_tone,
-                     dL_dout_color2, raw, sh_second, opts, want_colors=True, want_cov3D=True, depth=None):
-    """The checked backward call through ctypes -> the reference's eight, + what the optional blocks add (+ dL_dvalues [P] last with `depth`)."""
+                     dL_dout_color2, raw, sh_second, opts, want_colors=True, want_cov3D=True, depth=None, distortion=None):
+    """The checked backward call through ctypes -> the reference's eight, + what the optional blocks add (+ the distortion's dL_dvalues [P] with
+    `distortion`, + depth's dL_dvalues [P] last with `depth`)."""
     device, P, H, W = means3D.device, means3D.size(0), dL_dout_color.size(1), dL_dout_color.size(2)
     sh = _f32(sh, device)
     M = sh.size(1) if sh.numel() != 0 else 0
@@ -730,6 +799,7 @@ def _backward_ctypes(background, means3D, radii, colors, scales, rotations, scal
     dL_dcolors2 = alloc((P, 3), **f) if dual else None
     tone_grads, tone2_grads = (None if t is None else tuple(None if v is None else alloc((P, 3), **f) for v in t[:2]) for t in (sh_tone, sh_second))
     dL_dvalues = None if depth is None else alloc((P,), **f)   # (the library fills it)
+    dL_dvalues_t = None if distortion is None else alloc((P,), **f)   # (likewise)
     if P != 0:
         means3D, background, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, subpixel_offset, dL_dout_color = _f32s(
             device, means3D, background, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, subpixel_offset, dL_dout_color)
@@ -754,11 +824,20 @@ def _backward_ctypes(background, means3D, radii, colors, scales, rotations, scal
             block = _DepthGrad(C.sizeof(_DepthGrad), dL_ddepth.data_ptr(), None if values is None else values.data_ptr(), dL_dvalues.data_ptr())
             keep += [dL_ddepth, values, block]
             a.depth = C.pointer(block)
+        extras = None
+        if distortion is not None:   # wg_distortion_grad, carried by wg_backward_extras: wg_backward_args' size is pinned
+            dL_ddist, moments, source = distortion
+            dL_ddist, moments = dL_ddist.contiguous(), moments.contiguous()
+            values = None if isinstance(source, str) else source.contiguous()
+            block = _DistortionGrad(C.sizeof(_DistortionGrad), dL_ddist.data_ptr(), moments.data_ptr(), None if values is None else values.data_ptr(),
+                                    dL_dvalues_t.data_ptr())
+            extras = _BackwardExtras(C.sizeof(_BackwardExtras), C.pointer(block))
+            keep += [dL_ddist, moments, values, block]
         with torch.cuda.device(device):
-            status = _lib.wg_rasterize_backward_ex(C.byref(a))
+            status = _lib.wg_rasterize_backward_ex(C.byref(a)) if extras is None else _lib.wg_rasterize_backward_with(C.byref(a), C.byref(extras))
         _check(status, "wg_rasterize_backward")
     out = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
-    last = () if depth is None else (dL_dvalues,)
+    last = (() if distortion is None else (dL_dvalues_t,)) + (() if depth is None else (dL_dvalues,))
     if sh_second is not None:
         return out + (tone_grads or (None, None)) + tone2_grads + last
     if dual:
@@ -942,6 +1021,65 @@ def render_depth(geomBuffer, binningBuffer, imageBuffer, num_rendered, P, image_
     with torch.cuda.device(device):
         _check(_lib.wg_render_depth(C.byref(a)), "wg_render_depth")
     return depth
+
+
+# ----------------------------------------------------------------------------------------------------------
+# The distortion pass (wg_render_distortion): the distortion term of a finished frame from the blend weights' centred moments.
+def _check_distortion_arguments(geomBuffer, binningBuffer, imageBuffer, num_rendered, P, image_height, image_width, source, means3D, campos,
+                                subpixel_offset):
+    """What render_distortion refuses: _check_depth_arguments' list with the distortion's own source messages."""
+    device = imageBuffer.device
+    check_distortion_source(source, P)
+    if isinstance(source, torch.Tensor):
+        if not source.is_cuda or source.device != device:
+            raise RuntimeError(DISTORTION_SOURCE_MSG)
+    else:
+        if means3D is None or campos is None:
+            raise RuntimeError('distortion source "distance" needs means3D and campos')
+        if means3D.dtype != torch.float32 or means3D.numel() != 3 * P or campos.dtype != torch.float32 or campos.numel() != 3:
+            raise RuntimeError("means3D must be float32 with 3 * P elements, campos float32 with 3")
+        if not means3D.is_cuda or means3D.device != device or not campos.is_cuda or campos.device != device:
+            raise RuntimeError("means3D and campos must live on the frame's HIP device")
+    if int(P) < 0 or int(num_rendered) < 0 or int(image_height) <= 0 or int(image_width) <= 0:
+        raise RuntimeError("P and num_rendered must not be negative, image_height and image_width must be positive")
+    if subpixel_offset is not None and subpixel_offset.numel() != 0 and (
+            subpixel_offset.dtype != torch.float32 or subpixel_offset.numel() != 2 * int(image_height) * int(image_width) or subpixel_offset.device != device):
+        raise RuntimeError("subpixel_offset must be float32 with H * W * 2 elements on the frame's HIP device")
+    if not (geomBuffer.is_cuda and binningBuffer.is_cuda and imageBuffer.is_cuda):
+        raise RuntimeError("the frame's buffers must live on a HIP device")
+
+
+def render_distortion(geomBuffer, binningBuffer, imageBuffer, num_rendered, P, image_height, image_width, source, means3D=None, campos=None,
+                      subpixel_offset=None, options=None, moments=False, debug=False):
+    """distortion (float32 [H, W]) of the finished frame these three buffers belong to: sum_{j<i} w_i w_j (v_i - v_j)^2 over the pairs the frame
+    blended, w = alpha * T, as A Q' - D'^2 of the moments centred on each pixel's first blended v (wg_render_distortion) -- one launch on torch's
+    current stream that only reads the frame.  source: "distance" (v = |means3D - campos|, both then required) or a float32 [P] device tensor.
+    moments=True: -> (distortion, moments [4, H, W] = the planes A, D', Q', c), what the frame's backward call takes with the distortion's
+    cotangent (rasterize_gaussians_backward(distortion=)).  subpixel_offset / options: the frame's."""
+    opts = resolve_call_options(options)
+    H, W = int(image_height), int(image_width)
+    if _torch_ext is not None:
+        return _torch_ext.render_distortion(geomBuffer, binningBuffer, imageBuffer, int(num_rendered), int(P), H, W, source, means3D, campos,
+                                            subpixel_offset, opts, bool(moments), bool(debug))
+    _check_distortion_arguments(geomBuffer, binningBuffer, imageBuffer, num_rendered, P, H, W, source, means3D, campos, subpixel_offset)
+    device = imageBuffer.device
+    dist = torch.empty((H, W), dtype=torch.float32, device=device)   # both fully written by the library
+    mom = torch.empty((4, H, W), dtype=torch.float32, device=device) if moments else None
+    distance = isinstance(source, str)
+    keep = [t.contiguous() if t is not None and t.numel() != 0 else None
+            for t in ((means3D if distance else None), (campos if distance else None), (None if distance else source), subpixel_offset)]
+    a = _DistortionArgs()
+    a.struct_size = C.sizeof(a)
+    a.P, a.R, a.width, a.height, a.debug = int(P), int(num_rendered), W, H, int(bool(debug))
+    if int(P) != 0:
+        a.geom_buffer, a.binning_buffer, a.image_buffer = geomBuffer.data_ptr(), binningBuffer.data_ptr(), imageBuffer.data_ptr()
+    a.means3D, a.campos, a.values, a.subpixel_offset = (None if t is None else t.data_ptr() for t in keep)
+    ob = _CallOptions(*opts)
+    a.options = C.pointer(ob)
+    a.out_distortion, a.out_moments, a.stream = dist.data_ptr(), None if mom is None else mom.data_ptr(), _stream(device)
+    with torch.cuda.device(device):
+        _check(_lib.wg_render_distortion(C.byref(a)), "wg_render_distortion")
+    return (dist, mom) if moments else dist
 
 
 # ----------------------------------------------------------------------------------------------------------

@@ -81,7 +81,8 @@ class _RasterizeGaussians(torch.autograd.Function):
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                 sh_mul=None, sh_offset=None, sh_pre_clamp_max=None, sh_post_clamp_max=None, binning_capacity=None, colors_precomp2=None,
                 filter_3D=None, sh_second=False, sh_mul2=None, sh_offset2=None, sh_pre_clamp_max2=None, sh_post_clamp_max2=None, call_options=None,
-                colour_gradients_only=None, grad_mode=True, contributions=None, depth_grad=False, return_depth=None):
+                colour_gradients_only=None, grad_mode=True, contributions=None, distortion_grad=False, return_distortion=None, depth_grad=False,
+                return_depth=None):
         rs = raster_settings
         native_args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                        rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.kernel_size, rs.subpixel_offset,
@@ -120,6 +121,15 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raise Exception(_C.DEPTH_CAPACITY_MSG)
         elif depth_grad:
             raise Exception("depth_grad=True is the gradient of the depth output: pass return_depth too")
+        # the distortion pass over the finished frame (wg_render_distortion) and its gradient (wg_distortion_grad): refused like the depth pass's
+        if return_distortion is not None:
+            _C.check_distortion_source(return_distortion, means3D.shape[0])
+            if distortion_grad and _C.distortion_grad_refused(ctx.colour_only, ctx.call_options, binning_capacity is not None):
+                raise Exception(_C.DISTORTION_GRAD_MSG)
+            if binning_capacity is not None:
+                raise Exception(_C.DISTORTION_CAPACITY_MSG)
+        elif distortion_grad:
+            raise Exception("distortion_grad=True is the gradient of the distortion output: pass return_distortion too")
         # the contribution pass over the finished frame (wg_render_contributions): (stats, mask) or None; refused now, before anything is rendered
         contrib_mask = None
         if contributions is not None:
@@ -158,8 +168,22 @@ class _RasterizeGaussians(torch.autograd.Function):
         # radii and accumulation take no gradient (reference backward signature (ctx, grad_out_color, _, _), :117): do not let
         # autograd materialise P- and H*W-sized zero tensors for them on every backward pass
         ctx.set_materialize_grads(False)
+        ctx.distortion = return_distortion is not None
+        ctx.distortion_grad = ctx.distortion and bool(distortion_grad)
+        ctx.distortion_source = None
+        distortion = moments = None
+        if ctx.distortion:
+            # one more walk over the frame just finished, reading its buffers only: the blend weights' centred moments per pixel and A Q' - D'^2 of
+            # them.  With distortion_grad the moments are kept for the frame's backward call; without it none are written
+            source = return_distortion.detach() if isinstance(return_distortion, torch.Tensor) else return_distortion
+            distortion = _call_native(lambda *a: _C.render_distortion(*a, options=ctx.call_options, moments=ctx.distortion_grad, debug=rs.debug),
+                                      (geom_buf, binning_buf, img_buf, num_rendered, means3D.shape[0], rs.image_height, rs.image_width, source,
+                                       means3D.detach(), rs.campos, rs.subpixel_offset), rs.debug, "snapshot_distortion.dump", "the distortion pass")
+            if ctx.distortion_grad:
+                distortion, moments = distortion
+                ctx.distortion_source = source
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf, binning_buf, img_buf,
-                              *((filter_3D, opacities) if ctx.raw else ()))
+                              *((filter_3D, opacities) if ctx.raw else ()), *((moments,) if ctx.distortion_grad else ()))
 
         accumulation = None
         if rs.return_accumulation:
@@ -171,6 +195,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.depth = return_depth is not None
         ctx.depth_grad = ctx.depth and bool(depth_grad)
         ctx.depth_source = None
+        nondiff = []
         if ctx.depth:
             # one more walk over the frame just finished, reading its buffers only (whichever call served it: a full one or, with geometry
             # reuse, a recolouring): the image stays differentiable as before, depth takes no gradient
@@ -181,8 +206,14 @@ class _RasterizeGaussians(torch.autograd.Function):
             if ctx.depth_grad:   # the scalars go to the backward call as the forward pass read them ("distance": the call's means3D and campos)
                 ctx.depth_source = return_depth.detach() if isinstance(return_depth, torch.Tensor) else return_depth
             else:
-                ctx.mark_non_differentiable(depth)
+                nondiff.append(depth)
             out += (depth,)
+        if ctx.distortion:   # the call's LAST output, behind depth
+            if not ctx.distortion_grad:
+                nondiff.append(distortion)
+            out += (distortion,)
+        if nondiff:   # (one call: a second would replace the first's list)
+            ctx.mark_non_differentiable(*nondiff)
         if contributions is not None:
             # and one more that combines what each Gaussian contributed to it into the caller's arrays; the frame is only read, the output
             # tuple is what it was, nothing here takes a gradient
@@ -195,11 +226,17 @@ class _RasterizeGaussians(torch.autograd.Function):
         return out
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, _grad_accumulation, grad_out_color2=None, grad_depth=None):
-        if ctx.depth and ctx.sh_second is None and not ctx.dual:   # (color, radii, accumulation, depth): the fourth cotangent is depth's
-            grad_depth, grad_out_color2 = grad_out_color2, None
+    def backward(ctx, grad_out_color, _grad_radii, _grad_accumulation, grad_out_color2=None, *more):
+        # the cotangents behind the reference's three, in the outputs' order: the second image's, depth's, the distortion's -- each only where the
+        # forward call returned the output (the fourth is whichever of them comes first)
+        more = [grad_out_color2] + list(more)
+        grad_out_color2 = more.pop(0) if (ctx.sh_second is not None or ctx.dual) and more else None
+        grad_depth = more.pop(0) if ctx.depth and more else None
+        grad_dist = more.pop(0) if ctx.distortion and more else None
         if not ctx.depth_grad:   # (depth was marked non-differentiable: its cotangent is always None)
             grad_depth = None
+        if not ctx.distortion_grad:
+            grad_dist = None
         rs = ctx.raster_settings
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom_buf, binning_buf, img_buf = ctx.saved_tensors[:10]
         zeros = lambda: torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
@@ -211,7 +248,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         extra = dict(options=ctx.call_options, colour_gradients_only=ctx.colour_only)   # the frame's forward call's
         if ctx.colour_only:   # dL_dcolors and nothing else: the geometry inputs' .grad stay as they were
             g_colors = _call_native(lambda *a: _C.rasterize_gaussians_backward(*a, **extra), native_args, rs.debug, "snapshot_bw.dump", "backward")[1]
-            return (None, None, None, g_colors) + (None,) * 23
+            return (None, None, None, g_colors) + (None,) * 25
         # dL_dcolors / dL_dcov3D are intermediates of a plain SH + scales/rotations call: wanted only where the input takes a gradient (what is not
         # wanted comes back as None, neither allocated nor stored)
         extra["want"] = (ctx.needs_input_grad[3], ctx.needs_input_grad[7])
@@ -225,6 +262,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             extra["sh_second"] = ctx.sh_second
         if grad_depth is not None:   # a loss on depth: one more walk adds its gradient into the record (None: today's call, no walk)
             extra["depth"] = (grad_depth, ctx.depth_source)
+        if grad_dist is not None:    # a loss on the distortion: likewise, with the moments its forward pass left
+            extra["distortion"] = (grad_dist, ctx.saved_tensors[-1], ctx.distortion_source)
         res = _call_native(lambda *a: _C.rasterize_gaussians_backward(*a, **extra), native_args, rs.debug, "snapshot_bw.dump", "backward")
         (g_means2D, g_colors, g_opacities, g_means3D, g_cov3Ds, g_sh, g_scales, g_rotations) = res[:8]
         g_mul = g_offset = g_colors2 = g_mul2 = g_offset2 = None
@@ -240,18 +279,25 @@ class _RasterizeGaussians(torch.autograd.Function):
             g_mul, g_offset = shaped(res[8], ctx.sh_tone[0]), shaped(res[9], ctx.sh_tone[1])
         # the scalars' gradient, where return_depth was a tensor that takes one (its place among forward()'s inputs: the last)
         g_values = None
-        if grad_depth is not None and isinstance(ctx.depth_source, torch.Tensor) and ctx.needs_input_grad[26]:
+        if grad_depth is not None and isinstance(ctx.depth_source, torch.Tensor) and ctx.needs_input_grad[28]:
             g_values = res[-1].view(ctx.depth_source.shape)
+        # ... and the distortion's: in front of depth's in the native result where both blocks went
+        g_values_t = None
+        if grad_dist is not None and isinstance(ctx.distortion_source, torch.Tensor) and ctx.needs_input_grad[26]:
+            g_values_t = res[-2 if grad_depth is not None else -1].view(ctx.distortion_source.shape)
         # order of forward()'s inputs; None for raster_settings, the clamp constants and the options
         return (g_means3D, g_means2D, g_sh, g_colors, g_opacities, g_scales, g_rotations, g_cov3Ds, None, g_mul, g_offset, None, None, None, g_colors2, None,
-                None, g_mul2, g_offset2, None, None, None, None, None, None, None, g_values)
+                None, g_mul2, g_offset2, None, None, None, None, None, None, None, g_values_t, None, g_values)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                         sh_mul=None, sh_offset=None, sh_pre_clamp_max=None, sh_post_clamp_max=None, binning_capacity=None, colors_precomp2=None,
                         filter_3D=None, sh_second=False, sh_mul2=None, sh_offset2=None, sh_pre_clamp_max2=None, sh_post_clamp_max2=None, call_options=None,
-                        *, colour_gradients_only=None, return_depth=None, depth_grad=False, contributions=None, contribution_mask=None):
+                        *, colour_gradients_only=None, return_depth=None, depth_grad=False, contributions=None, contribution_mask=None,
+                        return_distortion=None, distortion_grad=False):
     _C._colour_mode(colour_gradients_only)   # (an unknown string: ValueError, before anything touches the device)
+    if isinstance(return_distortion, str):
+        _C.check_distortion_source(return_distortion)   # (likewise)
     # contributions=: the keyword, else what an open `with collect_contributions(stats, mask)` block of this thread still holds -- its FIRST
     # forward call takes it (handed back if that call raises)
     taken = False
@@ -265,7 +311,8 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                                          raster_settings, sh_mul, sh_offset, sh_pre_clamp_max, sh_post_clamp_max, binning_capacity, colors_precomp2,
                                          filter_3D, sh_second, sh_mul2, sh_offset2, sh_pre_clamp_max2, sh_post_clamp_max2, call_options,
                                          colour_gradients_only, torch.is_grad_enabled(),
-                                         None if contributions is None else (contributions, contribution_mask), bool(depth_grad), return_depth)
+                                         None if contributions is None else (contributions, contribution_mask), bool(distortion_grad), return_distortion,
+                                         bool(depth_grad), return_depth)
     except BaseException:
         if taken:
             _contrib.restore_pending(contributions, contribution_mask)
@@ -315,8 +362,27 @@ class GaussianRasterizer(nn.Module):
                 sh_offset2: Optional[torch.Tensor] = None, sh_pre_clamp_max2: Optional[float] = None,
                 sh_post_clamp_max2: Optional[float] = None, exact_compositing: Optional[bool] = None,
                 deterministic_backward: Optional[bool] = None, grad_record: Optional[bool] = None,
-                colour_gradients_only=None, return_depth=None, depth_grad: bool = False, contributions=None, contribution_mask=None):
-        """`contributions=stats` (keyword-only, beyond the reference): a `ContributionStats(P, device)`.  After the frame is finished, one more
+                colour_gradients_only=None, return_depth=None, depth_grad: bool = False, contributions=None, contribution_mask=None,
+                return_distortion=None, distortion_grad: bool = False):
+        """`return_distortion=` (keyword-only, beyond the reference): `"distance"` or a float32 [P] device tensor of per-Gaussian scalars v, the two
+        sources of `return_depth`.  The call then returns what it returns otherwise PLUS, as its LAST output (behind `depth` when both are asked
+        for), `distortion` ([H, W] float32): the Mip-NeRF 360 / 2DGS distortion term of the frame just rendered,
+        sum_{j<i} w_i w_j (v_i - v_j)^2 with w = alpha * T over the (pixel, Gaussian) pairs the frame blended -- the frame's own decisions, no
+        background term, no normalisation, 0 for a pixel without a contributor.  One more walk over the finished frame's lists
+        (wg_render_distortion) sums the weights' moments CENTRED on each pixel's first blended v and forms A Q' - D'^2: the term is invariant
+        under a shift of v, and the centred sums do not cancel where a `colors_precomp = (1, v, v^2)` render's A Q - D^2 does in float32 (thin
+        surfaces far from the camera).  Not clamped: a last-bit negative value can come out.  Works under `torch.no_grad()`, with every colour
+        source, on a frame served by geometry reuse, beside `return_depth` / `depth_grad` and `contributions=`; refused with
+        `binning_capacity`; an unknown string raises ValueError before anything touches the device.  None (the default): nothing new runs.
+        `distortion_grad=True` (with `return_distortion=`): `distortion` is DIFFERENTIABLE -- with respect to the call's geometry inputs (with
+        `filter_3D=` the RAW parameters), to a `return_distortion` tensor that requires grad, and in `"distance"` mode to `means3D` through
+        v = |means3D - campos| as well.  The forward pass then keeps four [H, W] planes of moments, and a loss on the distortion costs ONE more
+        per-tile walk in the frame's backward call, adding into the gradient record like `depth_grad`'s (wg_distortion_grad), behind it when both
+        are present; `means2D.grad[:, 2]` accumulates |q_dist| beside |q_image|.  A backward pass in which the distortion took no gradient
+        launches no walk.  Refused at forward time with `colour_gradients_only`, `deterministic_backward=1`, `grad_record=0` and
+        `binning_capacity`, and without `return_distortion`.  False (the default): the output takes no gradient and no moments are kept.
+
+        `contributions=stats` (keyword-only, beyond the reference): a `ContributionStats(P, device)`.  After the frame is finished, one more
         walk over its lists combines into `stats`, per Gaussian and over the (pixel, Gaussian) pairs this call blended, the largest blend
         weight w = alpha * T (`max_weight`), the number of pairs (`hits`) and the sum of floor(w * 2^32) (`weight_sum_q32`), and
         `stats.views` goes up by one (wg_render_contributions).  Integer atomics only: two sweeps give the same bits.  The published
@@ -393,6 +459,8 @@ class GaussianRasterizer(nn.Module):
         features' raw tensor, `mul`, `offset / C0`, and 1.0 for both clamps) without the P x 48 intermediate tensors -- and return
         gradients for `shs` (raw), `sh_mul` and `sh_offset` ([P, 3] each)."""
         _C._colour_mode(colour_gradients_only)   # (an unknown string: ValueError, before anything touches the device)
+        if isinstance(return_distortion, str):
+            _C.check_distortion_source(return_distortion)   # (likewise)
         if (shs is None) == (colors_precomp is None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if colors_precomp2 is not None and colors_precomp is None:
@@ -415,4 +483,4 @@ class GaussianRasterizer(nn.Module):
             None if exact_compositing is None and deterministic_backward is None and grad_record is None else
             dict(exact_compositing=exact_compositing, deterministic_backward=deterministic_backward, grad_record=grad_record),
             colour_gradients_only=colour_gradients_only, return_depth=return_depth, depth_grad=depth_grad,
-            contributions=contributions, contribution_mask=contribution_mask)
+            contributions=contributions, contribution_mask=contribution_mask, return_distortion=return_distortion, distortion_grad=distortion_grad)

@@ -66,6 +66,20 @@ class _DepthArgs(C.Structure):  # wg_depth_args
                 [("options", C.POINTER(_CallOptions)), ("out_depth", _vp), ("debug", _i), ("stream", _vp)])
 
 
+class _DistortionArgs(C.Structure):  # wg_distortion_args
+    _fields_ = ([("struct_size", C.c_size_t)] + [(n, _i) for n in ("P", "R", "width", "height")] +
+                [(n, _vp) for n in ("geom_buffer", "binning_buffer", "image_buffer", "subpixel_offset", "values", "means3D", "campos")] +
+                [("options", C.POINTER(_CallOptions)), ("out_distortion", _vp), ("out_moments", _vp), ("debug", _i), ("stream", _vp)])
+
+
+class _DistortionGrad(C.Structure):  # wg_distortion_grad
+    _fields_ = [("struct_size", C.c_size_t), ("dL_ddistortion", _vp), ("moments", _vp), ("values", _vp), ("dL_dvalues", _vp)]
+
+
+class _BackwardExtras(C.Structure):  # wg_backward_extras: what a backward call carries beyond wg_backward_args (whose size is pinned)
+    _fields_ = [("struct_size", C.c_size_t), ("distortion", C.POINTER(_DistortionGrad))]
+
+
 class _ContribArgs(C.Structure):  # wg_contrib_args
     _fields_ = ([("struct_size", C.c_size_t)] + [(n, _i) for n in ("P", "R", "width", "height")] +
                 [(n, _vp) for n in ("geom_buffer", "binning_buffer", "image_buffer", "subpixel_offset", "pixel_mask")] +
