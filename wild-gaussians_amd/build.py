@@ -62,6 +62,9 @@ SOURCES = {
                                        # (include/wg_densify_prune.h), which switches contraction off for itself with a pragma
     "sh_eval.hip": [],                 # fused eval_sh fwd/bwd (include/wg_sh_eval.h)
     "adam.hip": ["-ffp-contract=off"],   # fused Adam step (include/wg_adam.h); no FMA contraction: torch's update, op for op
+    "adam/adam_rows.hip": ["-ffp-contract=off"],   # the Adam step over a device-side list of visible rows (include/wg_adam_rows.h): adam.hip's
+                                                   # update restated under adam.hip's flags, so that a listed row has the dense kernel's bits; in a
+                                                   # subdirectory like the other opt-ins
     "appearance/mlp.hip": [],          # fused appearance MLP fwd/bwd on float32 MFMA (include/wg_appearance_mlp.h); in a subdirectory: the
                                        # top level of csrc/ is the list of files bench.py's byte model names
     "appearance/colour.hip": [],       # fused toned-colour operator over mlp.hip's tile walk (include/wg_appearance_colour.h)
@@ -87,7 +90,7 @@ SOURCES = {
                                        # float32 before it is widened into a float64 sum, which no contraction can cross
 }
 HEADERS = ["wg_common.h", "wg_alpha.h", "wg_sort.h", "wg_act.h", os.path.join("distortion", "distortion.h"), os.path.join(INCLUDE, "wg_rasterizer.h"), os.path.join(INCLUDE, "wg_knn.h"),
-           os.path.join(INCLUDE, "wg_ssim.h"), os.path.join(INCLUDE, "wg_activations.h"), os.path.join(INCLUDE, "wg_densify.h"), os.path.join(INCLUDE, "wg_adam.h"), os.path.join(INCLUDE, "wg_sh_eval.h"),
+           os.path.join(INCLUDE, "wg_ssim.h"), os.path.join(INCLUDE, "wg_activations.h"), os.path.join(INCLUDE, "wg_densify.h"), os.path.join(INCLUDE, "wg_adam.h"), os.path.join(INCLUDE, "wg_adam_rows.h"), os.path.join(INCLUDE, "wg_sh_eval.h"),
            os.path.join(INCLUDE, "wg_filter3d.h"), os.path.join(INCLUDE, "wg_densify_prune.h"), os.path.join(INCLUDE, "wg_msssim.h"),
            os.path.join(INCLUDE, "wg_appearance_mlp.h"), os.path.join(INCLUDE, "wg_appearance_colour.h"),
            os.path.join(INCLUDE, "wg_appearance_rows.h"),

@@ -51,6 +51,12 @@ The same operator over the rows that reach the image only, forward and backward,
     offset_mul = appearance_mlp((features[..., :3], gembedding), weights, shared=aembedding, rows=rows)             # [P, 6], zeros at unlisted rows
     with appearance_rows(rows): ...                           # the forward that apply_optins(appearance_mlp=True) swaps in uses the list
 
+The optimizer step over the same list: only the Gaussians the frame reached are updated, every other row keeps parameter and moments
+(include/wg_adam_rows.h; 3D-GS's sparse_adam, gsplat's SelectiveAdam):
+
+    from wg_fused_gaussians import VisibleRowsAdam
+    optimizer = VisibleRowsAdam.adopt(model.optimizer);  optimizer.visible(radii);  optimizer.step()
+
 The toned precomputed colours of one image (method.py:1555, :1557, :890-900, :1592-1598) from its [E] appearance embedding in one kernel, with the
 embedding's gradient alone coming back in one kernel and a finishing launch, over the visible rows only (include/wg_appearance_colour.h); and the
 loop of optimize_embedding (method.py:1786-1815) around it:
@@ -198,11 +204,30 @@ class FusedAdam(torch.optim.Adam):
 
     @torch.no_grad()
     def step(self, closure=None):
+        return self._step_dense(closure)
+
+    def _step_dense(self, closure):   # not `step` itself: torch wraps every class's `step` with its hooks, which a subclass must not run twice
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         by_device = {}
+        for _, p, d, g in self._descriptors():
+            by_device.setdefault(p.device, []).append((d, g))   # g: keeps a contiguous copy alive until the launch is queued
+        self._launch_dense(by_device)
+        return loss
+
+    @staticmethod
+    def _launch_dense(by_device):
+        for dev, items in by_device.items():
+            arr = (_AdamTensor * len(items))(*[d for d, _ in items])
+            with torch.cuda.device(dev):
+                _native._check(_lib.wg_fused_adam(len(items), arr, torch.cuda.current_stream(dev).cuda_stream), "wg_fused_adam")
+
+    def _descriptors(self):
+        """One step's bookkeeping for every parameter that has a gradient -- the checks, torch's lazy state, the step counter, the version
+        counters -- -> [(group, parameter, its wg_adam_tensor, the contiguous gradient)] in group order.  Nothing is launched."""
+        out = []
         for group in self.param_groups:
             if group.get("amsgrad") or group.get("maximize") or group.get("decoupled_weight_decay"):
                 raise NotImplementedError("wg_fused_gaussians.FusedAdam: amsgrad / maximize / decoupled_weight_decay are not implemented")
@@ -238,16 +263,110 @@ class FusedAdam(torch.optim.Adam):
                 # the step's scalars in double precision, rounded once when they enter the struct -- as torch's Python computes them
                 d = _AdamTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), beta2, 1.0 - beta1, 1.0 - beta2,
                                 lr / (1.0 - beta1 ** step), (1.0 - beta2 ** step) ** 0.5, float(group["eps"]), float(group["weight_decay"]))
-                by_device.setdefault(p.device, []).append((d, g))   # g: keeps a contiguous copy alive until the launch is queued
+                out.append((group, p, d, g))
                 # the kernel writes p, m and v behind torch's back: say so, as an in-place torch op would (autograd's saved-tensor
                 # checks and the rasterizer binding's geometry reuse both read the version counter)
                 torch.autograd.graph.increment_version(p)
                 torch.autograd.graph.increment_version(m)
                 torch.autograd.graph.increment_version(v)
-        for dev, items in by_device.items():
-            arr = (_AdamTensor * len(items))(*[d for d, _ in items])
+        return out
+
+
+# ---- the same step over the rows a frame reached (include/wg_adam_rows.h, csrc/adam/adam_rows.hip) ---------------------------------------
+class _AdamRowsTensor(C.Structure):   # wg_adam_rows_tensor
+    _fields_ = [("t", _AdamTensor), ("width", C.c_int64)]
+
+
+_lib.wg_adam_rows_step.restype = _i
+_lib.wg_adam_rows_step.argtypes = [_i, C.POINTER(_AdamRowsTensor), C.c_int64, _vp, C.c_int64, _vp, _vp]
+
+
+class VisibleRowsAdam(FusedAdam):
+    """``FusedAdam`` whose ``step()`` updates, in the per-Gaussian groups, only the rows of a list: the Gaussians with ``radii > 0`` in the
+    frame just rendered -- 3D-GS's ``sparse_adam`` / gsplat's ``SelectiveAdam`` (include/wg_adam_rows.h):
+
+        optimizer = VisibleRowsAdam(groups, lr=0.0, eps=1e-15)        # or VisibleRowsAdam.adopt(an existing torch.optim.Adam)
+        optimizer.visible(radii)                                       # the list for the NEXT step() only; or step(rows=...)
+        optimizer.step()
+
+    A listed row receives ``FusedAdam``'s update, bit for bit.  An unlisted row keeps its parameter AND both moments, whatever its gradient
+    holds: dense Adam would decay the moments and move the parameter along them although the frame gave it a gradient of exactly zero, and
+    a loss term that gives invisible Gaussians a non-zero gradient (a regulariser over all scales, say) is ignored for them.  Results
+    differ from dense Adam by design.
+
+    ``per_gaussian``: the ``name``s of the groups whose parameters are ``[P, ...]`` tensors of one Gaussian per row.  Every other group
+    (per-image appearance embeddings, the MLP, the uncertainty head) and every group of a step without a list takes the dense kernel, in
+    the same call of ``step()``.  The list is a ``VisibleRows`` or the rasterizer's int32 ``radii`` (compacted on the device by
+    ``VisibleRows.from_radii`` when the step needs it; no host wait).  ``step()`` consumes the list: the next step without one is
+    ``FusedAdam.step()``.  A per-Gaussian parameter whose row count differs from the list's raises before anything is launched (the stale
+    list after a densification); one without a gradient is skipped before that check, as torch does -- after the caller's
+    ``densify_and_prune`` replaced the parameters between ``backward()`` and ``step()`` the step is a no-op for them and the list is dropped.
+
+    The step count: a parameter's ``step`` advances once per ``step()`` that hands it to a kernel, with or without a list, and the bias
+    correction follows this GLOBAL count, as in gsplat's ``SelectiveAdam`` -- not a count per row.  (The list's length lives on the device;
+    a step whose list turns out empty there still counts.)  ``row_steps`` / ``dense_steps`` count the steps taken with / without a list.
+    It is still a ``torch.optim.Adam``: ``adopt``, the state layout, state dicts and the lr schedule are FusedAdam's."""
+
+    PER_GAUSSIAN = ("xyz", "features_dc", "opacities", "scales", "rotations", "embeddings", "features_rest")
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, *, per_gaussian=PER_GAUSSIAN, **kw):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **kw)
+        self.per_gaussian = frozenset(per_gaussian)
+        self.row_steps = 0
+        self.dense_steps = 0
+        self._pending_rows = None
+
+    def visible(self, rows):
+        """Hand over the list for the NEXT ``step()`` only: a ``VisibleRows``, an int32 ``radii`` tensor, or None to withdraw it."""
+        if rows is not None and not isinstance(rows, VisibleRows):
+            if not (torch.is_tensor(rows) and rows.is_cuda and rows.dtype == torch.int32 and rows.dim() == 1):
+                raise RuntimeError("wg_fused_gaussians.VisibleRowsAdam: rows must be a VisibleRows or a 1-D int32 radii tensor on a HIP device")
+            rows = rows.detach()
+        self._pending_rows = rows
+
+    @torch.no_grad()
+    def step(self, closure=None, *, rows=None):
+        if rows is not None:
+            self.visible(rows)
+        rows, self._pending_rows = self._pending_rows, None   # consumed, whatever happens below
+        if rows is None:
+            self.dense_steps += 1
+            return self._step_dense(closure)
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        listed = rows.P if isinstance(rows, VisibleRows) else rows.numel()
+        for group in self.param_groups:   # before any bookkeeping and any launch
+            if group.get("name") not in self.per_gaussian:
+                continue
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.dim() < 1 or (listed is not None and p.shape[0] != listed):
+                    raise RuntimeError(f"wg_fused_gaussians.VisibleRowsAdam: the row list was built for {listed} rows, parameter "
+                                       f"'{group.get('name')}' has {p.shape[0] if p.dim() else 'no'} -- a list from before a densification?")
+                if p.device != (rows.index.device if isinstance(rows, VisibleRows) else rows.device):
+                    raise RuntimeError("wg_fused_gaussians.VisibleRowsAdam: the row list and the parameters are on different devices")
+                if listed is None:   # an explicit index list of unknown P: every per-Gaussian tensor must at least agree
+                    listed = p.shape[0]
+        dense, sparse = {}, []
+        for group, p, d, g in self._descriptors():
+            if group.get("name") in self.per_gaussian:
+                sparse.append((_AdamRowsTensor(d, p.numel() // p.shape[0] if p.shape[0] else 1), g))
+            else:
+                dense.setdefault(p.device, []).append((d, g))
+        if sparse:
+            if not isinstance(rows, VisibleRows):
+                rows = VisibleRows.from_radii(rows)
+            arr = (_AdamRowsTensor * len(sparse))(*[d for d, _ in sparse])
+            dev = rows.index.device
             with torch.cuda.device(dev):
-                _native._check(_lib.wg_fused_adam(len(items), arr, torch.cuda.current_stream(dev).cuda_stream), "wg_fused_adam")
+                _native._check(_lib.wg_adam_rows_step(len(sparse), arr, listed, rows.index.data_ptr(), rows.M,
+                                                      None if rows.count is None else rows.count.data_ptr(),
+                                                      torch.cuda.current_stream(dev).cuda_stream), "wg_adam_rows_step")
+        self._launch_dense(dense)
+        self.row_steps += 1
         return loss
 
 

@@ -28,6 +28,16 @@ needs the few-line edits INTEGRATION.md lists.  What IS swapped, each with the r
                         parameters and buffers are re-registered and `optimizer.state` re-keyed as the reference does (a new nn.Parameter
                         per group, the state moved to it).  `GaussianModel.reset_opacity` (method.py:1249-1278) ->
                         wg_fused_gaussians.reset_opacity.  The split's draw is torch.randn on the device
+  visible_adam          (OFF by default: results differ from dense Adam BY DESIGN; only with adam, else ValueError)
+                        `_setup_optimizers`, and an optimizer that already exists on `model`, adopt into wg_fused_gaussians.VisibleRowsAdam
+                        instead of FusedAdam, and `GaussianModel._render_internal` (the caller's own or edited_module's) is wrapped: a render
+                        in training mode with grad mode on hands its `radii` to `self.optimizer.visible(...)`, and the `optimizer.step()` that
+                        follows (method.py:2019) updates, in the seven per-Gaussian groups, only the rows with radii > 0 (3D-GS's sparse_adam,
+                        gsplat's SelectiveAdam; include/wg_adam_rows.h).  Unlisted Gaussians keep parameter and both moments; a loss term that
+                        gives invisible Gaussians a non-zero gradient is ignored for them; the bias correction follows the global step count.
+                        The list lasts one step.  Evaluation renders and `optimize_embedding` run in eval mode and leave none behind; in the
+                        densification step the caller's `densify_and_prune` replaces the parameters before `step()`, which then skips them
+                        (no gradient) and drops the list
   uncertainty_metrics   (OFF by default: results move within float32 rounding, and callers' logged metrics must not move unasked)
                         `method.msssim` (method.py:171-187) and `method.ssim_down` (:126-135), which UncertaintyModel._compute_losses
                         looks up as module globals on every step -> wg_fused_ssim.msssim / ssim_down (forward only); calls they do not
@@ -116,7 +126,7 @@ import torch
 
 def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True, densification_stats: bool = True, activations: bool = True,
                  eval_sh: bool = True, geometry_reuse: bool = True, edited_module=None, filter_3d: bool = False, densify: bool = False,
-                 embedding_optim=False, uncertainty_loss: bool = False, uncertainty_backbone: bool = False,
+                 visible_adam: bool = False, embedding_optim=False, uncertainty_loss: bool = False, uncertainty_backbone: bool = False,
                  uncertainty_feature_cache: bool = False, appearance_mlp: bool = False, uncertainty_metrics: bool = False):
     """-> a function that restores everything that was replaced.  `model`: an already constructed GaussianModel (e.g.
     `WildGaussians(...).model`) whose existing optimizer should be adopted too.
@@ -128,6 +138,8 @@ def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True
     if uncertainty_feature_cache and not uncertainty_backbone:
         raise ValueError("uncertainty_feature_cache needs uncertainty_backbone: only the fused extractor is bit-reproducible, so that a cached "
                          "feature map is the one a recomputation would give")
+    if visible_adam and not adam:   # before anything is swapped
+        raise ValueError("visible_adam needs adam: it is the fused optimizer that takes the row list")
     saved = []
 
     def swap(obj, name, new):
@@ -139,14 +151,15 @@ def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True
         swap(method_module, "ssim", wg_fused_ssim.ssim)
     if adam:
         orig_setup = GM._setup_optimizers
+        adam_class = FG.VisibleRowsAdam if visible_adam else FG.FusedAdam
 
         def _setup_optimizers(self):
             orig_setup(self)
-            self.optimizer = FG.FusedAdam.adopt(self.optimizer)
+            self.optimizer = adam_class.adopt(self.optimizer)
         swap(GM, "_setup_optimizers", _setup_optimizers)
-        if model is not None and getattr(model, "optimizer", None) is not None and not isinstance(model.optimizer, FG.FusedAdam):
+        if model is not None and getattr(model, "optimizer", None) is not None and not isinstance(model.optimizer, adam_class):
             saved.append((model, "optimizer", model.optimizer))
-            model.optimizer = FG.FusedAdam.adopt(model.optimizer)
+            model.optimizer = adam_class.adopt(model.optimizer)
     if densification_stats:
         def add_densification_stats(self, viewspace_point_tensor, update_filter):
             # the kernel's visibility test is radii > 0: the boolean filter IS that test's result (method.py:1622), as 0 / 1
@@ -323,6 +336,17 @@ def apply_optins(method_module, model=None, ssim: bool = True, adam: bool = True
         for name in ("ssim", "eval_sh"):   # the edited function looks module-level names up in ITS module: hand it the swapped ones
             swap(edited, name, getattr(method_module, name))   # (undo() puts its own back: the module object is cached in sys.modules)
         swap(GM, "_render_internal", edited.GaussianModel._render_internal)
+
+    if visible_adam:
+        inner_render = GM._render_internal   # whatever is in place now: the caller's own, or edited_module's
+
+        def _render_internal(self, *args, **kwargs):
+            out = inner_render(self, *args, **kwargs)
+            optimizer = getattr(self, "optimizer", None)
+            if self.training and torch.is_grad_enabled() and isinstance(optimizer, FG.VisibleRowsAdam):
+                optimizer.visible(out["radii"])   # for the step that follows this frame only; compacted on the device when that step runs
+            return out
+        swap(GM, "_render_internal", _render_internal)
 
     reuse_before = None
     if geometry_reuse:
